@@ -23,6 +23,11 @@ the whole job.
 
 One "step" = one ADMM iteration.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`
+= milliseconds of one timed step, and what describes them).  `--dump-outputs DIR` writes what the
+last timed step computed to DIR/<name>.npy (dump_outputs).  Everything else below is measured
+only with `--full`:
+
 The line's `configs` object carries the other BASELINE.json configurations as one GPU sees them
 (config 1; config 3 as one of its 8 image shards; config 4 with and without BacktrackStandard;
 config 5), each timed the same way, with a parity figure against a run of the UNMODIFIED reference
@@ -821,6 +826,31 @@ def time_to_tol(cbpdn, H, W, K, N, device, lmbda=0.01):
     return out
 
 
+DUMP_MAX_VALUES = 1 << 22       # 16 MB of float32: the coefficient sample of --dump-outputs
+
+
+def dump_outputs(out_dir, b, steps):
+    """--dump-outputs: what a caller of the timed solve() receives, as DIR/<name>.npy -- the
+    coefficient map Y after the last timed step (all of it up to DUMP_MAX_VALUES values, else a
+    fixed seeded sample of that many: the flat indices of RandomState(0), sorted) and the
+    per-iteration statistics of the timed steps except the wall-clock `Time` (float64; none under
+    --fastsolve, which records no statistics)."""
+    from sporco_amd.admm import cbpdn
+    os.makedirs(out_dir, exist_ok=True)
+    Y = np.asarray(cbpdn.ConvBPDN.getmin(b)).reshape(-1)
+    if Y.size > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.RandomState(0).randint(0, Y.size, DUMP_MAX_VALUES))
+        np.save(os.path.join(out_dir, 'Y_sample.npy'), Y[idx].astype(np.float32))
+    else:
+        np.save(os.path.join(out_dir, 'Y.npy'), Y.astype(np.float32))
+    del Y
+    timed = b.itstat[-steps:]
+    for f in (type(b).IterationStats._fields if timed else ()):
+        v = [getattr(s, f) for s in timed]
+        if f != 'Time' and all(isinstance(x, (int, float, np.number)) for x in v):
+            np.save(os.path.join(out_dir, 'itstat_%s.npy' % f), np.asarray(v, dtype=np.float64))
+
+
 def respawn_under_torchrun(args):
     """`python bench.py --gpus N` (N > 1) without a launcher: start the N ranks ourselves."""
     import socket
@@ -861,7 +891,15 @@ def main():
                     help='iterations of the same solver after the timed ones (`steady_state`)')
     ap.add_argument('--parity-only', action='store_true',
                     help='run the parity gate alone and print its JSON (what the main run spawns)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: parity gate, steady state, per-kernel '
+                         'roofline, the other option set, the other configurations, time to '
+                         'tolerance and the CPU baseline (a plain run times the headline alone)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(respawn_under_torchrun(args))
@@ -929,10 +967,10 @@ def main():
     # since round 5 the library places its concurrently written arrays by measurement --
     # DESIGN.md 4.7, `roofline.placement` below -- and the separation only keeps the runs alike)
     parity = None
-    if rank == 0 and not args.no_parity:
-        if args.parity_only:
-            print(json.dumps(parity_gate(cbpdn, H, W, K, args.parity_iters, local_rank)))
-            return
+    if args.parity_only:
+        print(json.dumps(parity_gate(cbpdn, H, W, K, args.parity_iters, local_rank)))
+        return
+    if rank == 0 and args.full and not args.no_parity:
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), '--parity-only', '--size', str(H),
@@ -1011,6 +1049,45 @@ def main():
         return b, elapsed
 
     b, elapsed = timed_run(args.fastsolve)
+    if args.dump_outputs and not args.full and rank == 0:
+        dump_outputs(args.dump_outputs, b, args.steps)
+    ms_per_step = 1e3 * elapsed / args.steps
+    names = {False: 'default options (AutoRho, stats every iteration)',
+             True: 'FastSolve, AutoRho off'}
+    line = {
+        'metric': 'ConvBPDN ADMM iterations/s',
+        'value': args.steps / elapsed * world,
+        'unit': 'iterations/s (%dx%d, K=%d, N=%d per GPU; summed over GPUs)' % (H, W, K, N),
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': ms_per_step,
+        'higher_is_better': True,
+        'scaling': 'weak',
+        'vs_baseline': None,
+        'dtype': 'f32',
+        'data': 'synthetic',
+        'config': {'workload': 'admm.cbpdn.ConvBPDN %dx%d greyscale, K=%d 8x8 filters, '
+                               'N=%d images per GPU, lambda=0.05, %s'
+                               % (H, W, K, N, names[bool(args.fastsolve)]),
+                   'global_images': N * world, 'parallelism': 'image-shard x%d' % world},
+    }
+    loop = ('device-driven (sporco_amd_csc_admm_run): residuals, rho schedule and stopping test on '
+            'the device, host enqueues only') if not os.environ.get('SPORCO_AMD_HOST_LOOP') \
+        else 'host-driven (one sporco_amd_csc_admm_iter call per iteration)'
+    if not args.full:
+        # the headline alone: nothing after the timed steps but this line
+        del b
+        if rank == 0:
+            line.update({'ranks': rank_stats or None, 'loop': loop})
+            line['summary'] = {'value': line['value'], 'ms_per_step': ms_per_step,
+                               'ranks': ({k: rank_stats[k] for k in ('ms_per_step_slowest_rank',
+                                                                     'ms_per_step_fastest_rank', 'reducer')}
+                                         if rank_stats else None)}
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # the same solver object carried on for 100 more iterations: with default options rho moves
     # in most of the first 20-30 iterations (which invalidates the speculatively emitted row
     # spectra); what a user sees over the hundreds of iterations to tolerance is the rate after
@@ -1115,13 +1192,20 @@ def main():
             except Exception as e:      # noqa: BLE001 -- every rank fails alike (same shapes) or none
                 config3_sharded = {'error': '%s: %s' % (type(e).__name__, e)}
 
+    if args.dump_outputs:
+        # (reading Y back ends the timed solver's single-array state (ensure_yu), which would change
+        # every figure taken from that solver afterwards: a --full run dumps from a second run of the
+        # same warm-up and timed steps -- the iteration is deterministic, it computes the same arrays)
+        b, _ = timed_run(args.fastsolve)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, b, args.steps)
+        del b
+
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return
 
-    ms_per_step = 1e3 * elapsed / args.steps
-    its_per_s = args.steps / elapsed
     moved, alg = byte_model(H, W, 1, N, K)
     table = kernel_roofline(prof, moved, alg)
     dom = dominant(table)
@@ -1148,25 +1232,7 @@ def main():
                                      '(boxes of the pool differ by up to 8 %)'}
     E = H * W * N * K
     iter_alg_bytes = 40 * E                    # 10 float32 passes
-    names = {False: 'default options (AutoRho, stats every iteration)',
-             True: 'FastSolve, AutoRho off'}
-    line = {
-        'metric': 'ConvBPDN ADMM iterations/s',
-        'value': its_per_s * world,
-        'unit': 'iterations/s (%dx%d, K=%d, N=%d per GPU; summed over GPUs)' % (H, W, K, N),
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': ms_per_step,
-        'higher_is_better': True,
-        'scaling': 'weak',
-        'vs_baseline': None,
-        'dtype': 'f32',
-        'data': 'synthetic',
-        'config': {'workload': 'admm.cbpdn.ConvBPDN %dx%d greyscale, K=%d 8x8 filters, '
-                               'N=%d images per GPU, lambda=0.05, %s'
-                               % (H, W, K, N, names[bool(args.fastsolve)]),
-                   'global_images': N * world, 'parallelism': 'image-shard x%d' % world},
+    line.update({
         'steady_state': {'steps': steady_steps, 'value': steady_steps / elapsed_steady * world,
                          'ms_per_step': 1e3 * elapsed_steady / steady_steps,
                          'note': 'the same solver continued for %d more iterations after the timed '
@@ -1204,13 +1270,11 @@ def main():
                           'ms_per_step': 1e3 * elapsed2 / args.steps},
         'ranks': rank_stats or None,
         'parity': parity,
-        'loop': ('device-driven (sporco_amd_csc_admm_run): residuals, rho schedule and stopping '
-                 'test on the device, host enqueues only') if not os.environ.get('SPORCO_AMD_HOST_LOOP')
-                else 'host-driven (one sporco_amd_csc_admm_iter call per iteration)',
+        'loop': loop,
         'result_download_ms': download_ms,
         'kernels_ms_per_iter': {k: round(v[0] / prof_steps, 4) for k, v in prof.items() if v[1] > 0},
         'kernel_roofline': table,
-    }
+    })
     if config3_sharded is not None:
         line['configs'] = {'config3_sharded': config3_sharded}
     if world == 1 and args.configs != 'none':

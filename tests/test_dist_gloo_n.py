@@ -79,7 +79,7 @@ def test_bench_multi_rank_fields_under_gloo(tmp_path):
            '--master-addr', '127.0.0.1', '--master-port', '29641', os.path.join(REPO, 'bench.py'),
            '--gpus', '2', '--steps', '3', '--warmup', '1', '--size', '128', '--filters', '8', '--images', '1',
            '--steady-steps', '4', '--no-cpu-baseline', '--no-parity', '--no-time-to-tol', '--configs', 'config3',
-           '--tiny']
+           '--tiny', '--full']
     r = subprocess.run(cmd, env=env, timeout=1500, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith('{')]

@@ -8,8 +8,8 @@
 # Steps (each bounded by its own `timeout`):
 #   tests[:<pytest args>]  GPU test-suite (default: whole `-m gpu` suite)
 #   smoke                  __graft_entry__.smoke()
-#   bench[:<args>]         python bench.py <args>            -> bench[_<n>].json
-#   quick[:<args>]         bench.py without CPU baseline / time-to-tol / parity / side configs
+#   bench[:<args>]         python bench.py --full <args>     -> bench[_<n>].json
+#   quick[:<args>]         bench.py --full without CPU baseline / time-to-tol / parity / side configs
 #   stats[:<args>]         rocprofv3 --kernel-trace --stats of the quick bench -> kernel_stats.csv
 #   pmc                    FETCH_SIZE and WRITE_SIZE passes (separate runs) + hbm_traffic_bytes.json
 #   sq                     two SQ counter passes of the quick bench -> pmc_sq_{1,2}.csv
@@ -23,7 +23,7 @@ TAG=$1; shift
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 export TMPDIR=/tmp
-QUICK="--no-cpu-baseline --no-time-to-tol --no-parity --configs none"
+QUICK="--full --no-cpu-baseline --no-time-to-tol --no-parity --configs none"
 n=0
 summ() { python $R/tools/rocpd_summary.py "$(find $1 -name '*.db' | head -1)" "$2" > /dev/null 2>&1 || echo "no rocpd summary for $2"; }
 for step in "$@"; do
@@ -37,7 +37,7 @@ for step in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | grep -v amdgpu.ids | tail -3 | tee $O/smoke.txt ;;
     bench)
-      timeout 1500 python bench.py $arg > $O/bench_$n.json 2> $O/bench_$n.err; tail -c 600 $O/bench_$n.err; head -c 700 $O/bench_$n.json; echo ;;
+      timeout 1500 python bench.py --full $arg > $O/bench_$n.json 2> $O/bench_$n.err; tail -c 600 $O/bench_$n.err; head -c 700 $O/bench_$n.json; echo ;;
     quick)
       timeout 600 python bench.py $QUICK $arg 2>/dev/null | tail -1 > $O/quick_$n.json; head -c 500 $O/quick_$n.json; echo ;;
     stats)

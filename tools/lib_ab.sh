@@ -9,7 +9,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 MODE=$1; CONFIGS=$2; shift 2
-Q="--no-cpu-baseline --no-time-to-tol --no-parity --configs $CONFIGS"
+Q="--full --no-cpu-baseline --no-time-to-tol --no-parity --configs $CONFIGS"
 n=0
 for tag in "$@"; do
   n=$((n+1))

@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QUICK = ['--no-cpu-baseline', '--no-time-to-tol', '--no-parity', '--configs', 'none']
+QUICK = ['--full', '--no-cpu-baseline', '--no-time-to-tol', '--no-parity', '--configs', 'none']
 dummies = [int(x) for x in sys.argv[1:]] or [0, 2050, 4100, 6150, 8200, 12300, 16400, 24600, 2, 258]
 
 for mb in dummies:
