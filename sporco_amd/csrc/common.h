@@ -187,4 +187,30 @@ inline int current_device_cus() {
     return cache[dev];
 }
 
+// A 1.0f in the memory of the CURRENT device, allocated on first use there and cached per device
+// id as above: the weight array that the row kernels' general epilogue reads when none is set.
+inline const float *device_one() {
+    static float *cache[64] = {nullptr};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!cache[dev]) {
+        const float v = 1.0f;
+        float *one = nullptr;
+        SA_HIP(hipMalloc((void **)&one, sizeof(float)));
+        SA_HIP(hipMemcpy(one, &v, sizeof(float), hipMemcpyHostToDevice));
+        cache[dev] = one;
+    }
+    return cache[dev];
+}
+
+// Launch of a kernel with `lds` bytes of dynamic LDS: its limit is raised to that once per device,
+// before the first launch there.
+template <auto KERNEL, typename A> void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &a) {
+    static PerDeviceOnce attr_set;
+    if (attr_set.first())
+        SA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, a);
+}
+
 }  // namespace sporco_amd

@@ -165,11 +165,12 @@ template <typename T> struct Csc : CscBase {
     int part_f_rows = 0;   // rows of part_f the last column pass wrote (tiles, or tiles x slabs)
     // fused row passes (csc_rows.h)
     bool rows_ok = false;
-    // Mixed-radix shape (round 6): H or W one of 320 / 384 / 448 / 480 -- the register-resident kernels
-    // exist for a single-channel dictionary: ConvBPDN (scalar or array L1Weight, NonNegCoef,
-    // NoBndryCross), ConvBPDNJoint, ConvBPDNGradReg, AddMaskSim with K <= 256; FISTA and the tile-major
-    // dictionary update with K <= 64 (csc_rows_mr.hip, csc_pgm_mr.hip, csc_fused.h); LinSolveCheck,
-    // mask decoupling and consensus stay on the generic chain for such a handle.
+    // Mixed-radix shape: H or W = 16 N1, N1 in regfft.h SA_MR_LENGTHS (160 ... 480) -- the
+    // register-resident kernels exist for a single-channel dictionary: ConvBPDN (scalar or array
+    // L1Weight, NonNegCoef, NoBndryCross), ConvBPDNJoint, ConvBPDNGradReg, AddMaskSim and mask
+    // decoupling with K <= 256; FISTA and the tile-major dictionary update with K <= 64
+    // (csc_rows_body.inc, csc_pgm_body.inc, csc_fused.h); LinSolveCheck, multi-channel dictionaries
+    // and consensus stay on the generic chain for such a handle (include/sporco_amd.h).
     bool mr = false;
     bool mr_ok(const sporco_amd_admm_params &p) const {
         return !mr || (Cd == 1 && !wl21.ptr && !(p.flags & F_XRRS));
@@ -341,8 +342,8 @@ template <typename T> struct Csc : CscBase {
                   !sw.old_rows;
         mr = std::is_same<T, float>::value && (fused_mr_height(H) || rows_mr_width(W));
         if (mr && !((fused || fused_slabs) && rows_ok)) {
-            // (a mixed-radix side needs the register kernels on BOTH sides and K <= 64: otherwise
-            // the whole handle is a generic-chain one)
+            // (a mixed-radix side needs the register kernels on BOTH sides -- the column pass, or its
+            // slab form for K > 64: otherwise the whole handle is a generic-chain one)
             rows_ok = false;
             if (fused_mr_height(H)) fused = fused_slabs = false;
             mr = false;

@@ -146,9 +146,10 @@ void launch_mc_binv(hipStream_t st, const cx<T> *dft, T *bt, int64_t nrows, int 
 // tile-major 2-D spectrum of u0 (fields t, dft, sft, twA, H, W, CN, K, Ks, partials); t is only read.
 template <typename T> int64_t launch_cols_dualres(hipStream_t st, const FusedColsArgs<T> &a);
 
-// Mixed-radix heights (round 6): H = 320, 384, 448, 480 = 16 waves x 20 / 24 / 28 / 30 rows per thread
-// (regfft.h).  The plain column pass only (K <= 64, no gradient term, per-tile operands or stored
-// multipliers).
+// Mixed-radix heights: H = 16 N1 = 16 waves x N1 rows per thread, N1 in regfft.h SA_MR_LENGTHS
+// (160 ... 480).  The column pass with K <= 64 (the plain system, the gradient term, the multipliers
+// stored for mask decoupling; no per-tile operands), its slab form with K <= 256 (plain and gradient
+// term), the dual residual, and the kernels of csc_pgm.h.
 bool fused_mr_height(int H);
 // Host tables twA, twB for fused_cols_supported shapes: fused_twiddle_count(H) entries each
 // (H, except for the mixed-radix heights).

@@ -84,11 +84,8 @@ template <typename T> int64_t launch_pgm_fft_momentum(hipStream_t st, const PgmC
 template <typename T>
 int64_t launch_pgm_stats_slabs(hipStream_t st, const PgmColsArgs<T> &a, double *partials2);
 
-// Mixed-radix heights (csc_fused.h fused_mr_height: H = 16 x {10 ... 30}; csc_pgm_mr.hip): the three
-// column kernels above with that many rows per thread, K <= 64.
-// plain: the forward transform alone (launch_cols_fft).
-int64_t launch_pgm_grad_ifft_mr(hipStream_t st, const PgmColsArgs<float> &a);
-int64_t launch_pgm_fft_momentum_mr(hipStream_t st, const PgmColsArgs<float> &a, bool plain);
-int64_t launch_ccmod_grad_tiled_mr(hipStream_t st, const CcmodTiledArgs<float> &a);
+// Heights of the kernels above: 128, 256, 512 (K <= 64 for pgm_grad_ifft, K <= 256 for the others),
+// and the mixed-radix heights (csc_fused.h fused_mr_height: H = 16 N1, N1 in regfft.h
+// SA_MR_LENGTHS) with K <= 64.
 
 }  // namespace sporco_amd

@@ -1,3 +1,8 @@
-// csc_pgm_mr2.hip -- csc_pgm_mr.hip for the heights 16 x {21 ... 30} (second translation unit).
-#define SA_MR_PART 1
-#include "csc_pgm_mr.hip"
+// csc_pgm_mr2.hip -- the column launchers of csc_pgm_body.inc at the second half of the mixed-radix
+// heights (H = 16 N1, N1 in regfft.h SA_MR_LENGTHS_HI; csc_pgm_mr.hip: the first half).
+#include "csc_pgm_body.inc"
+
+namespace sporco_amd {
+#define SA_PGM_INSTANTIATE(n) SA_PGM_LAUNCHERS(template, n)
+SA_MR_LENGTHS_HI(SA_PGM_INSTANTIATE)
+}  // namespace sporco_amd

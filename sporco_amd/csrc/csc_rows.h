@@ -148,15 +148,14 @@ template <typename T> int64_t launch_rows_inv_prox_fwd(hipStream_t st, const Row
 // prox_l2, _lp.py:283-290) is a sum over the 16-lane rows of a wave (two permlane swaps).
 // Scalar weights, no NoBndryCross / AddMaskSim; K a multiple of 32.  partials[6] = the l2,1 sum.
 template <typename T> bool rows_joint_supported(int W, int C, int K);
-// Shapes the register-resident row kernels handle (float32, W in {128, 256, 512}, K even).
+// Shapes the register-resident row kernels handle (float32, K even): W in {128, 256, 512}, or a
+// mixed-radix width (rows_mr_width).
 template <typename T> bool rows_supported(int W, int K);
-// Mixed-radix widths (round 6): 320, 384, 448, 480 = 16 waves x 20 / 24 / 28 / 30 points per thread
-// (csc_rows_mr.hip).  Plain ConvBPDN options only: scalar weights, no NoBndryCross / AddMaskSim /
-// Joint; the launchers refuse anything else and the API layer keeps such calls on the generic chain.
+// Mixed-radix widths: W = 16 N1, N1 in regfft.h SA_MR_LENGTHS (160 ... 480), on 16 waves.  The same
+// options as the powers of two (weight arrays, NonNegCoef, NoBndryCross, AddMaskSim, Joint, the V
+// form, the proximal pass of FISTA) except the broadcast form and the striped spectrum
+// (RowsPostArgs::t_odd); the support matrix is in include/sporco_amd.h.
 bool rows_mr_width(int W);
-void launch_rows_fwd_mr(hipStream_t st, const RowsFwdArgs<float> &a);
-int64_t launch_rows_inv_post_mr(hipStream_t st, const RowsPostArgs<float> &a);
-int64_t launch_rows_inv_prox_fwd_mr(hipStream_t st, const RowsProxArgs<float> &a);
 // Host table for RowsFwdArgs::twA (W entries: [wave][point of the in-register transform]).
 template <typename T> void rows_twiddles(int W, cx<T> *twA);
 template <typename T> void launch_rows_fwd(hipStream_t st, const RowsFwdArgs<T> &a);

@@ -1,4 +1,8 @@
-// csc_rows_mr2.hip -- the mixed-radix row kernels of csc_rows_mr.hip for the lengths N1 = 21 ... 30
-// (a second translation unit: the two halves compile side by side).
-#define SA_MR_PART 1
-#include "csc_rows_mr.hip"
+// csc_rows_mr2.hip -- the row launchers of csc_rows_body.inc at the second half of the mixed-radix
+// widths (W = 16 N1, N1 in regfft.h SA_MR_LENGTHS_HI; csc_rows_mr.hip: the first half).
+#include "csc_rows_body.inc"
+
+namespace sporco_amd {
+#define SA_ROWS_INSTANTIATE(n) SA_ROWS_LAUNCHERS(template, n)
+SA_MR_LENGTHS_HI(SA_ROWS_INSTANTIATE)
+}  // namespace sporco_amd

@@ -121,9 +121,9 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Mixed-radix lengths (round 6): the in-register transform of N1 = 20, 24, 28 or 30 points, so
-// that lines of 16 N1 = 320, 384, 448, 480 points run on the register-resident kernels (the
-// second factor stays 16 = the waves of the workgroup).  Same conventions as the radix-2 pair
+// Mixed-radix lengths: the in-register transform of N1 points, N1 in SA_MR_LENGTHS below (10 ... 30),
+// so that lines of 16 N1 = 160 ... 480 points run on the register-resident kernels (the second
+// factor stays 16 = the waves of the workgroup).  Same conventions as the radix-2 pair
 // above: the forward transform is decimation in frequency -- natural in, DIGIT-reversed out:
 // position i holds X[mr_rev<N>(i)] --, the inverse one decimation in time from that order back to
 // natural; no reordering pass.  Radices are applied odd ones first (20 = 5.2.2, 24 = 3.2.2.2,
@@ -159,12 +159,32 @@ constexpr double mr_sin(int num, int den) { return mr_cos(4 * num - den, 4 * den
 
 // The supported lengths (one list for the kernels' instantiations, the launchers' switches and the
 // host tables): X(n) for every n.  16 n = 160, 192, 224, 240, 288, 320, 336, 384, 400, 432, 448, 480.
-#define SA_MR_LENGTHS(X) X(10) X(12) X(14) X(15) X(18) X(20) X(21) X(24) X(25) X(27) X(28) X(30)
+// The two halves are instantiated in translation units of their own (csc_rows_mr.hip /
+// csc_rows_mr2.hip, csc_pgm_mr.hip / csc_pgm_mr2.hip), which compile side by side.
+#define SA_MR_LENGTHS_LO(X) X(10) X(12) X(14) X(15) X(18) X(20)
+#define SA_MR_LENGTHS_HI(X) X(21) X(24) X(25) X(27) X(28) X(30)
+#define SA_MR_LENGTHS(X) SA_MR_LENGTHS_LO(X) SA_MR_LENGTHS_HI(X)
 constexpr bool mr_length(int n) {
 #define SA_MR_IS(m) if (n == m) return true;
     SA_MR_LENGTHS(SA_MR_IS)
 #undef SA_MR_IS
     return false;
+}
+
+// The line shapes of the register-resident kernels: n = 32 NW points on NW = 4, 8 or 16 waves, or
+// n = 16 N1 points on 16 waves for the mixed-radix N1.  Returns f(NW, N1) for the shape of n, the
+// two passed as std::integral_constant.
+template <typename F> auto with_line_shape(int n, F &&f) {
+    using std::integral_constant;
+    switch (n) {
+    case 128: return f(integral_constant<int, 4>(), integral_constant<int, 32>());
+    case 256: return f(integral_constant<int, 8>(), integral_constant<int, 32>());
+    case 512: return f(integral_constant<int, 16>(), integral_constant<int, 32>());
+#define SA_MR_CASE(m) case 16 * m: return f(integral_constant<int, 16>(), integral_constant<int, m>());
+    SA_MR_LENGTHS(SA_MR_CASE)
+#undef SA_MR_CASE
+    }
+    throw Error(-1, "line length not handled by the register-resident kernels");
 }
 // the radices of a length, in the order the forward transform applies them: odd ones first
 constexpr int mr_radix_at(int n, int s) {
