@@ -115,6 +115,8 @@ typedef struct {
 #define SPORCO_AMD_VAR_MU0 20  /* real  (H,W,C,N,1) ConvBPDNMaskDcpl: block 0 of U                 */
 #define SPORCO_AMD_VAR_DMY0 21 /* real  (H,W,C,N,1) mask-decoupling D-step: block 0 of Y           */
 #define SPORCO_AMD_VAR_DMU0 22 /* real  (H,W,C,N,1) mask-decoupling D-step: block 0 of U           */
+#define SPORCO_AMD_VAR_WML 23  /* real  (H,W,C,N,K) ConvBPDNInhib: lateral inhibition weights (inhib_update) */
+#define SPORCO_AMD_VAR_WMS 24  /* real  (H,W,C,N,K) ConvBPDNInhib: self inhibition weights                  */
 /* Dictionary-sized state of the D-step (pgm.ccmod.ConvCnstrMOD, admm.ccmod consensus Y =
  * DX): real (H,W,K) / complex (H,Wf,K).  Ids 19..31 are reserved. */
 #define SPORCO_AMD_VAR_DX 32      /* real  dictionary iterate X (zero-padded filters)    */
@@ -650,6 +652,43 @@ int sporco_amd_csc_mdcpl_init(sporco_amd_csc_t h, const void *S);
  * DFID = |W g0|^2 (twice the data fidelity, :2262-2268), L1 = |wl1 g1|_1; XRRS sums. */
 int sporco_amd_csc_mdcpl_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
                               double out[SPORCO_AMD_OUT_COUNT]);
+
+/* ---- ADMM with inhibition: sporco.admm.cbpdnin.ConvBPDNInhib (cbpdnin.py:28-352) -------------
+ * The iteration is the ConvBPDN one (sporco_amd_csc_admm_iter, or the staged calls) with an array
+ * l1 weight that sporco_amd_csc_inhib_update rewrites after every iteration: the thresholds
+ * T = lmbda wl1 + mu wml + gamma wms live in the handle's L1-weight array, so the y step is called
+ * with params.lmbda = 1 and needs X written (SPORCO_AMD_FLAG_KEEP_X, no FLAG_NO_X).
+ *
+ * The reference's window (cbpdnin.py:253-283) is separable: taps_rows act along H, taps_cols along
+ * W, tap t at offset t - ntaps / 2, circularly (a convolution, not a correlation: the taps of
+ * scipy's periodic windows are not symmetric).  1 <= ntaps_rows <= H, 1 <= ntaps_cols <= W; a
+ * folded dimN = 1 problem (H = 1) passes taps_rows = {1}.  Taps and Wg are doubles whatever the
+ * handle's dtype.
+ *
+ * setup: Wg (Ng, K) row-major grouping matrix, or NULL / Ng = 0: no lateral term.  want_self != 0:
+ * the self-inhibition weights exist.  The L1-weight array set before (sporco_amd_csc_set_l1_weight;
+ * none: 1) becomes wl1 of the formula above; the handle's L1-weight array is replaced by T,
+ * initialised to lmbda wl1 (wml = wms = 0, cbpdnin.py:229); VAR_WML / VAR_WMS are zeroed (only the
+ * live ones are allocated).  A later sporco_amd_csc_set_l1_weight ends the inhibition state.
+ * Single-channel dictionaries, no volume handles. */
+int sporco_amd_csc_inhib_setup(sporco_amd_csc_t h, const double *Wg, int32_t Ng,
+                               const double *taps_rows, int32_t ntaps_rows, const double *taps_cols,
+                               int32_t ntaps_cols, int32_t want_self, double lmbda);
+typedef struct {
+    double lmbda;    /* lmbda (times a scalar L1Weight)                                   */
+    double mu;       /* lateral term; > 0 updates VAR_WML (needs Wg), else it is left out */
+    double gamma;    /* self term; > 0 updates VAR_WMS (needs want_self), else left out   */
+    double smooth;   /* SmoothWeight: w <- smooth w + (1 - smooth) w_new                  */
+    uint32_t flags;  /* SPORCO_AMD_FLAG_GEVAL_Y: the sums are taken against Y, else X     */
+} sporco_amd_inhib_params;
+/* One launch (profile slot "inhib_update"): c = h (*) |X| per map (cbpdnin.py:310-317),
+ * lat_m = sum_g Wg[g,m] (sum_n Wg[g,n] c_n) - (sum_g Wg[g,m]) c_m (:319-320),
+ * self_m = c_m - h(0) |X_m| (:330-331), the smoothing of both (:322-323, :333-334), the new T, and
+ * out[SPORCO_AMD_OUT_L1] = sum |wl1 G|, out[SPORCO_AMD_OUT_L21] = sum |wml G|,
+ * out[SPORCO_AMD_OUT_RGR] = sum |wms G| with the updated weights (obfn_reg, :341-352); the other
+ * slots of out are zero. */
+int sporco_amd_csc_inhib_update(sporco_amd_csc_t h, const sporco_amd_inhib_params *p,
+                                double out[SPORCO_AMD_OUT_COUNT]);
 
 /* ---- online dictionary learning (sporco.dictlrn.onlinecdl.OnlineConvBPDNDictLearn.dstep,
  * onlinecdl.py:310-333) -------------------------------------------------------------------

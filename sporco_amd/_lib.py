@@ -18,6 +18,7 @@ VAR_T0, VAR_T1, VAR_T2, VAR_ZF = 13, 14, 15, 16
 VAR_CX, VAR_CU = 17, 18
 VAR_MY0, VAR_MU0 = 19, 20
 VAR_DMY0, VAR_DMU0 = 21, 22
+VAR_WML, VAR_WMS = 23, 24
 VAR_DX, VAR_DXF, VAR_DYF, VAR_DXFPRV, VAR_DYFPRV = 32, 33, 34, 35, 36
 VAR_DVF, VAR_DGF, VAR_DT0, VAR_DT1, VAR_DT2 = 37, 38, 39, 40, 41
 VAR_DSX, VAR_DSU = 42, 43
@@ -79,6 +80,7 @@ EXPORTS = (
     'sporco_amd_csc_dstep_init', 'sporco_amd_csc_dstep_iter', 'sporco_amd_csc_ccmod_sgd_step',
     'sporco_amd_csc_mdcpl_init', 'sporco_amd_csc_mdcpl_iter', 'sporco_amd_csc_dstep_md_init',
     'sporco_amd_csc_set_data_mask', 'sporco_amd_csc_masked_grad',
+    'sporco_amd_csc_inhib_setup', 'sporco_amd_csc_inhib_update',
     'sporco_amd_csc_profile', 'sporco_amd_csc_profile_read', 'sporco_amd_profile_slots',
     'sporco_amd_dev_malloc', 'sporco_amd_dev_free', 'sporco_amd_dev_upload',
     'sporco_amd_dev_download', 'sporco_amd_dev_axpby', 'sporco_amd_tikhonov_filter_dev',
@@ -140,6 +142,12 @@ class AdmmRecord(ctypes.Structure):
                 ('epri', ctypes.c_double), ('edua', ctypes.c_double), ('rho', ctypes.c_double),
                 ('u_scale', ctypes.c_double), ('seconds', ctypes.c_double),
                 ('k', ctypes.c_int32), ('stop', ctypes.c_int32)]
+
+
+class InhibParams(ctypes.Structure):
+    """sporco_amd_inhib_params: scalars of one inhibition-weight update."""
+    _fields_ = [('lmbda', ctypes.c_double), ('mu', ctypes.c_double), ('gamma', ctypes.c_double),
+                ('smooth', ctypes.c_double), ('flags', ctypes.c_uint32)]
 
 
 REDUCE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
@@ -285,6 +293,8 @@ def load(path=None):
         'sporco_amd_csc_cns_iter': [vp, ctypes.POINTER(CnsParams), dptr],
         'sporco_amd_csc_ccmod_sgd_step': [vp, dbl, i32, i32, i32, dptr],
         'sporco_amd_csc_mdcpl_init': [vp, vp],
+        'sporco_amd_csc_inhib_setup': [vp, dptr, i32, dptr, i32, dptr, i32, i32, dbl],
+        'sporco_amd_csc_inhib_update': [vp, ctypes.POINTER(InhibParams), dptr],
         'sporco_amd_csc_mdcpl_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_dstep_init': [vp, vp],
         'sporco_amd_csc_dstep_md_init': [vp, vp, vp],
@@ -661,6 +671,31 @@ class Solver(object):
     def mdcpl_iter(self, params):
         out = self._out()
         check(self._lib.sporco_amd_csc_mdcpl_iter(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def inhib_setup(self, Wg, taps_rows, taps_cols, want_self, lmbda):
+        """ConvBPDNInhib state (sporco_amd_csc_inhib_setup): ``Wg`` (Ng, K) or None, the window
+        taps along H and W; the handle's L1-weight array becomes the thresholds."""
+        K = self.dims[4]
+        tr = np.ascontiguousarray(taps_rows, dtype=np.float64).ravel()
+        tc = np.ascontiguousarray(taps_cols, dtype=np.float64).ravel()
+        dp = ctypes.POINTER(ctypes.c_double)
+        if Wg is None:
+            wg, ng = None, 0
+        else:
+            wg = np.ascontiguousarray(Wg, dtype=np.float64)
+            if wg.ndim != 2 or wg.shape[1] != K:
+                raise ValueError("Wg must be (groups, filters) = (Ng, %d), not %s" % (K, wg.shape))
+            ng = wg.shape[0]
+        check(self._lib.sporco_amd_csc_inhib_setup(
+            self._h, None if wg is None else wg.ctypes.data_as(dp), ng, tr.ctypes.data_as(dp),
+            tr.size, tc.ctypes.data_as(dp), tc.size, 1 if want_self else 0, float(lmbda)))
+
+    def inhib_update(self, lmbda, mu, gamma, smooth, flags):
+        """One inhibition-weight update (sporco_amd_csc_inhib_update); returns the sums."""
+        p = InhibParams(float(lmbda), float(mu), float(gamma), float(smooth), int(flags))
+        out = self._out()
+        check(self._lib.sporco_amd_csc_inhib_update(self._h, ctypes.byref(p), out))
         return list(out)
 
     def admm_iter_dev(self, params, out_dev_ptr):

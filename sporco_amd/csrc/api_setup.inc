@@ -83,6 +83,7 @@
         before_state_change();   // a pending X of the fused PGM step depends on the weights
         if (which == 2) ams_bits_valid = false;
         if (which == 3) have_wdat = w != nullptr;
+        if (which == 0) inhib_drop();   // (the L1-weight array held the inhibition thresholds)
         Weight<T> &dst = which == 0 ? wl1 : (which == 1 ? wl21 : (which == 2 ? wams : wdat));
         T *&buf = which == 0 ? wl1_buf : (which == 1 ? wl21_buf : (which == 2 ? wams_buf : wdat_buf));
         if (buf) {

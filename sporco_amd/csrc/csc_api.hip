@@ -25,7 +25,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                            "finalize",         "pgm_elementwise",  "other",
                                            "admm_persist_run",
                                     "setcoef_rows",     "setcoef_cols",     "ccmod_grad_tiled",
-                                    "fft_c2r_vpost",    "fft_c2r_vpost_emit"};
+                                    "fft_c2r_vpost",    "fft_c2r_vpost_emit",
+                                    "inhib_update"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -414,6 +415,7 @@ template <typename T> struct Csc : CscBase {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(st);
         place_release_spares();
+        inhib_release();
         big_free(gemit);
         if (part_vpost) (void)hipFree(part_vpost);
         big_free(cols_out[0]);
@@ -598,6 +600,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_consensus.inc"
 #include "api_maskdcpl.inc"
 #include "api_dstep.inc"
+#include "api_inhib.inc"
 };
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

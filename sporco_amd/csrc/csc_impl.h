@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "csc_fused.h"
+#include "csc_inhib.h"
 #include "csc_kernels.h"
 #include "csc_pgm.h"
 #include "csc_rows.h"
@@ -84,6 +85,7 @@ enum ProfSlot {
     PS_CCMOD_GRAD,              // ... and the gradient over tiles (ccmod_grad_tiled + group sum)
     PS_C2R_VPOST,               // generic chain: c2r row pass + epilogue of the single-array state in one
     PS_C2R_VPOST_EMIT,          // kernel (fft.h fft_c2r_vpost), ... + the next iteration's row spectrum
+    PS_INHIB,                   // ConvBPDNInhib: the inhibition-weight update (csc_inhib.h)
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -212,6 +214,9 @@ struct CscBase {
     virtual void dstep_md_init(const void *Y0, const void *S) = 0;
     virtual void dstep_iter(const sporco_amd_dstep_params &p, double *out_dev) = 0;
     virtual void fft_var(int rvar, int cvar, bool inverse) = 0;
+    virtual void inhib_setup(const double *Wg, int Ng, const double *taps_h, int nth, const double *taps_w,
+                             int ntw, bool want_self, double lmbda) = 0;
+    virtual void inhib_update(const sporco_amd_inhib_params &p, double *out_dev) = 0;
     virtual void read_out(const double *out_dev, double *out_host) = 0;
     double *out_dev_default = nullptr;
     Profiler prof;
@@ -254,7 +259,7 @@ static bool var_is_dict_sized(int var) {
 }
 
 static bool var_is_valid(int var) {
-    return (var >= 0 && var <= SPORCO_AMD_VAR_DMU0) ||
+    return (var >= 0 && var <= SPORCO_AMD_VAR_WMS) ||
            (var >= SPORCO_AMD_VAR_DX && var < SPORCO_AMD_VAR_COUNT);
 }
 
