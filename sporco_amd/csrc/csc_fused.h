@@ -90,18 +90,21 @@ template <typename T> void launch_gram_rows(hipStream_t st, const cx<T> *z, T *o
 // g1t_out[wf][h] from dft, ghh, ghw, wg, mu, rho.
 template <typename T> void launch_grad_g1(hipStream_t st, const FusedColsArgs<T> &a);
 
-// 64 < K <= 256 filters (NH = ceil(K/64) slabs, the last one possibly partial): a tile of all K filters does not fit the register file
-// of one workgroup, so the X-step column pass runs as two kernels over (tile, 64-filter
-// slab) pairs and exchanges only the partial inner products sum_k Df yuf through `qpart`:
-//   cols_fwd_partial    t <- FFT_H(t);            qpart[tile][slab][f] = sum_{k in slab} Df yuf
-//   cols_sm_apply_inv   q = sum_slab qpart;  xf = yuf + conj(Df)(Sf - q)/(gram + rho);
-//                       t <- IFFT_H(xf);  data-fidelity partials (slab 0 only)
-// (12 float32 passes per ADMM iteration instead of 10.)  Uses the FusedColsArgs fields plus:
+// 64 < K <= 256 filters (NH = ceil(K/64) slabs, the last one possibly partial): a tile of all K
+// filters does not fit the register file of one workgroup, so the X-step column pass runs on NH
+// cooperating workgroups per tile, one per 64-filter slab, in ONE launch.  Each keeps its slab of
+// the spectrum in registers, and they exchange only the partial inner products sum_k Df yuf
+// through `qpart`:
+//   phase 1   t <- FFT_H(t) (in registers);  qpart[tile][slab][f] = sum_{k in slab} Df yuf, flagged
+//             per (tile, slab) with the launch's sequence number
+//   phase 2   q = sum_slab qpart;  xf = yuf + conj(Df)(Sf - q)/(gram + rho);
+//             t <- IFFT_H(xf);  data-fidelity partials (slab 0 only)
+// (two X-sized passes, as the K <= 64 kernel.)  Uses the FusedColsArgs fields plus:
 template <typename T> struct FusedSlabArgs {
     FusedColsArgs<T> c;
     cx<T> *qpart;   // (Wf*CN, NH, H) complex
-    // the one-launch form (launch_cols_slab_coop): per (tile, slab) flags that the slab's
-    // partial sums of launch `coop_seq` are in qpart, and a host-visible error word
+    // per (tile, slab) flags that the slab's partial sums of launch `coop_seq` are in qpart, and a
+    // host-visible error word
     unsigned *coop_flags = nullptr;
     unsigned coop_seq = 0;
     int *coop_err = nullptr;
@@ -111,16 +114,13 @@ template <typename T> struct FusedSlabArgs {
     T pgm_inv_L = T(0);
     cx<T> *pgm_ey = nullptr;
 };
-// Both kernels above as ONE launch of cooperating slab workgroups (csc_fused.hip): two X-sized
-// passes instead of four.  Returns the number of tiles.
+// The column pass by cooperating slab workgroups (csc_fused_kernels.inc).  Returns the number of tiles.
 template <typename T> int64_t launch_cols_slab_coop(hipStream_t st, const FusedSlabArgs<T> &a);
 // pgm_grad_ifft of csc_pgm.h for 64 < K <= 256 by the same cooperating slab workgroups:
 // t = IFFT_H(Yf - conj(Df)(sum_k Df Yf - Sf) / L), partials[tile] = sum_f |sum_k Df Yf - Sf|^2.
 // Uses c.{t, dft, sft, twA, twB, H, W, CN, K, partials}, qpart, the coop fields and the pgm ones.
 template <typename T> int64_t launch_pgm_grad_slabs(hipStream_t st, const FusedSlabArgs<T> &a);
 template <typename T> bool fused_slabs_supported(int H, int K);
-template <typename T> void launch_cols_fwd_partial(hipStream_t st, const FusedSlabArgs<T> &a);
-template <typename T> int64_t launch_cols_sm_apply_inv(hipStream_t st, const FusedSlabArgs<T> &a);
 
 // Multi-channel dictionary (Cd = 2..4 channels in D and S, one coefficient channel): the
 // column pass with the Cd rank-one terms in registers (csc_fused_mc.hip).  Woodbury form of the
@@ -147,10 +147,13 @@ void launch_mc_binv(hipStream_t st, const cx<T> *dft, T *bt, int64_t nrows, int 
 template <typename T> int64_t launch_cols_dualres(hipStream_t st, const FusedColsArgs<T> &a);
 
 // Mixed-radix heights: H = 16 N1 = 16 waves x N1 rows per thread, N1 in regfft.h SA_MR_LENGTHS
-// (160 ... 480).  The column pass with K <= 64 (the plain system, the gradient term, the multipliers
-// stored for mask decoupling; no per-tile operands), its slab form with K <= 256 (plain and gradient
-// term), the dual residual, and the kernels of csc_pgm.h.
+// (160 ... 480).  The column pass with K <= 64 (the plain system, the gradient term, or the multipliers
+// stored for mask decoupling; no per-tile operands, no 64-filter kernel on longer rows -- Kv), its
+// slab form with K <= 256 (plain and gradient term, run-time row stride; not launch_pgm_grad_slabs),
+// the dual residual, and the kernels of csc_pgm.h.  No multi-channel column pass.
 bool fused_mr_height(int H);
+// The power-of-two heights: H = 32 NW on NW = 4, 8 or 16 waves.
+constexpr bool fused_pow2_height(int H) { return H == 128 || H == 256 || H == 512; }
 // Host tables twA, twB for fused_cols_supported shapes: fused_twiddle_count(H) entries each
 // (H, except for the mixed-radix heights).
 int fused_twiddle_count(int H);

@@ -51,7 +51,7 @@ constexpr size_t fused_lds_bytes(int NW, int LP) {
 // workgroup, each with its own control block); no stop test and no start-up stagger here then.
 // The statements live in csc_fused_body.inc and are included into fused_cols_kernel
 // (csc_fused.hip) and into this function.
-template <int N1, int NW, int LPARAM, int KC, bool GRAD, bool KRT, bool PER_TILE, int DBG,
+template <int N1, int NW, int LP, int KC, bool GRAD, bool KRT, bool PER_TILE, int DBG,
           bool PERSIST, int AOFF>
 __device__ __forceinline__ void fused_cols_body(const FusedColsArgs<float> &a,
                                                 SA_ARGS_PTR_T(FusedColsArgs<float>) afix) {

@@ -1,7 +1,7 @@
 // csc_fused_body.inc -- the statements of the column pass (see csc_fused_body.h), included
 // textually into the two functions that run it, so that fused_cols_kernel compiles exactly as
 // if it were written in place.  In scope where it is included: the template parameters N1, NW,
-// LPARAM, KC, GRAD, KRT, PER_TILE, DBG, the constants PERSIST and AOFF, the arguments `a`, and
+// LP, KC, GRAD, KRT, PER_TILE, DBG, the constants PERSIST and AOFF, the arguments `a`, and
 // the pointer `afix` (used when AOFF < 0 -- admm_persist_kernel, where the tile and its sum also
 // change hands between workgroups of the launch: agent-scope accesses, gfx950_intrin.h).
 
@@ -13,12 +13,11 @@
     constexpr bool MR = mr_length(N1);
     constexpr int J = MR ? (N1 > NW ? 2 : 1) : N1 / NW;   // stage-2 lines per thread (each NW points)
     constexpr int LBW = ilog2(NW);
-    static_assert(!MR || (NW == 16 && LPARAM == 1), "mixed-radix heights: 16 waves, one line per group");
+    static_assert(!MR || (NW == 16 && LP == 1), "mixed-radix heights: 16 waves, one line per group");
     // The two LDS exchanges and the solve between them are pipelined over groups
     // of LP lines (FP = LP*NW values of f1): a group leaves the register tile,
     // is transformed / solved / transformed back by the waves that own its
     // lines, and returns to the same registers; the rest of the tile stays put.
-    constexpr int LP = LPARAM;
     constexpr int FP = LP * NW, Q = J / LP;
     static_assert(J % LP == 0, "lines per group must divide the lines per thread");
     static_assert(FP * NW * 64 <= kExchUnitsMax, "exchange group too large");

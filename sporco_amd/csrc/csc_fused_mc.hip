@@ -28,12 +28,11 @@ constexpr size_t mc_lds_bytes(int NW, int LP) {
     return sizeof(f2) * LP * NW * NW * 64 + sizeof(double) * 16;
 }
 
-template <int N1, int NW, int LPARAM, int KC, int CC>
+template <int N1, int NW, int LP, int KC, int CC>
 __global__ void __launch_bounds__(NW * 64) fused_cols_mc_kernel(const FusedMcArgs<float> a) {
     constexpr int H = N1 * NW;
     constexpr int J = N1 / NW;
     constexpr int LB1 = ilog2(N1), LBW = ilog2(NW);
-    constexpr int LP = LPARAM;
     constexpr int FP = LP * NW, Q = J / LP;
     static_assert(CC >= 2 && CC <= 4, "2 to 4 dictionary channels");
     const int tid = threadIdx.x;
@@ -248,47 +247,40 @@ __global__ void __launch_bounds__(256) mc_binv_kernel(const cf *__restrict__ dft
     }
 }
 
-template <int N1, int NW, int LP, int KC, int CC>
-void launch_mc_inst(hipStream_t st, const FusedMcArgs<float> &a) {
-    static PerDeviceOnce attr_set;
-    if (attr_set.first()) {
-        SA_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void *>(&fused_cols_mc_kernel<N1, NW, LP, KC, CC>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)mc_lds_bytes(NW, LP)));
-    }
+template <int NW, int N1, int KC, int CC> void fused_mc_variant(hipStream_t st, const FusedMcArgs<float> &a) {
+    constexpr int LP = 16 / NW;
     const int64_t wf_groups = ceil_div(a.W / 2 + 1, 8);
-    hipLaunchKernelGGL((fused_cols_mc_kernel<N1, NW, LP, KC, CC>),
-                       dim3((unsigned)(wf_groups * 8 * a.N)), dim3(NW * 64), mc_lds_bytes(NW, LP),
-                       st, a);
+    launch_lds<&fused_cols_mc_kernel<N1, NW, LP, KC, CC>>(dim3((unsigned)(wf_groups * 8 * a.N)), dim3(NW * 64),
+                                                         mc_lds_bytes(NW, LP), st, a);
 }
-
-template <int CC> void launch_mc_cc(hipStream_t st, const FusedMcArgs<float> &a) {
-    if (a.H == 128) {
-        if (a.K == 64) launch_mc_inst<32, 4, 4, 64, CC>(st, a);
-        else launch_mc_inst<32, 4, 4, 0, CC>(st, a);
-    } else if (a.H == 256) {
-        if (a.K == 64) launch_mc_inst<32, 8, 2, 64, CC>(st, a);
-        else launch_mc_inst<32, 8, 2, 0, CC>(st, a);
+template <int NW, int N1, int KC> void fused_mc_kc(hipStream_t st, const FusedMcArgs<float> &a) {
+    switch (a.Cd) {
+    case 2: return fused_mc_variant<NW, N1, KC, 2>(st, a);
+    case 3: return fused_mc_variant<NW, N1, KC, 3>(st, a);
+    default: return fused_mc_variant<NW, N1, KC, 4>(st, a);
+    }
+}
+// One launcher on the column shape <NW, N1> (regfft.h with_line_shape)
+template <int NW, int N1> void fused_mc_launch(hipStream_t st, const FusedMcArgs<float> &a) {
+    // (the multi-channel kernel has no mixed-radix form: fused_mc_supported)
+    if constexpr (mr_length(N1)) {
+        SA_REQUIRE(false, "mixed-radix heights: no multi-channel column kernel");
     } else {
-        if (a.K == 64) launch_mc_inst<32, 16, 1, 64, CC>(st, a);
-        else launch_mc_inst<32, 16, 1, 0, CC>(st, a);
+        if (a.K == 64) fused_mc_kc<NW, N1, 64>(st, a);
+        else fused_mc_kc<NW, N1, 0>(st, a);
     }
 }
 
 }  // namespace
 
 template <> bool fused_mc_supported<float>(int H, int K, int Cd) {
-    return (H == 128 || H == 256 || H == 512) && K >= 1 && K <= 64 && Cd >= 2 && Cd <= 4;
+    return fused_pow2_height(H) && K >= 1 && K <= 64 && Cd >= 2 && Cd <= 4;
 }
 template <> bool fused_mc_supported<double>(int, int, int) { return false; }
 
 template <> int64_t launch_fused_cols_mc<float>(hipStream_t st, const FusedMcArgs<float> &a) {
     SA_REQUIRE(fused_mc_supported<float>(a.H, a.K, a.Cd), "shape not handled by the multi-channel column kernel");
-    switch (a.Cd) {
-    case 2: launch_mc_cc<2>(st, a); break;
-    case 3: launch_mc_cc<3>(st, a); break;
-    default: launch_mc_cc<4>(st, a); break;
-    }
+    regfft::with_line_shape(a.H, [&](auto nw, auto n1) { fused_mc_launch<nw.value, n1.value>(st, a); });
     SA_HIP(hipGetLastError());
     return (int64_t)(a.W / 2 + 1) * a.N;
 }

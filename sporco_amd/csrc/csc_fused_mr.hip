@@ -1,0 +1,8 @@
+// csc_fused_mr.hip -- the column launchers of csc_fused_kernels.inc at the first half of the mixed-radix
+// heights (H = 16 N1, N1 in regfft.h SA_MR_LENGTHS_LO; csc_fused_mr2.hip: the second half).
+#include "csc_fused_kernels.inc"
+
+namespace sporco_amd {
+#define SA_FUSED_INSTANTIATE(n) SA_FUSED_LAUNCHERS(template, n)
+SA_MR_LENGTHS_LO(SA_FUSED_INSTANTIATE)
+}  // namespace sporco_amd

@@ -71,7 +71,7 @@ void launch_ccmod_resid_sum(hipStream_t st, const CcmodTiledArgs<float> &a, int 
 
 // heights of the column kernels: 128, 256, 512 with 1 <= K <= kmax, the mixed-radix ones with K <= 64
 static bool pgm_shape_ok(int H, int K, int kmax) {
-    return K >= 1 && (fused_mr_height(H) ? K <= 64 : (H == 128 || H == 256 || H == 512) && K <= kmax);
+    return K >= 1 && (fused_mr_height(H) ? K <= 64 : fused_pow2_height(H) && K <= kmax);
 }
 
 template <> int64_t launch_pgm_grad_ifft<float>(hipStream_t st, const PgmColsArgs<float> &a) {

@@ -8,14 +8,6 @@ namespace sporco_amd {
 // points per thread of a supported line length: 32 for the powers of two, W / 16 for the
 // mixed-radix lengths (regfft.h SA_MR_LENGTHS)
 static int rows_n1(int W) { return rows_mr_width(W) ? W / 16 : kN1; }
-static int rows_rev(int N1, int i) {
-    switch (N1) {
-#define SA_MR_CASE(n) case n: return regfft::mr_rev<n>(i);
-    SA_MR_LENGTHS(SA_MR_CASE)
-#undef SA_MR_CASE
-    default: return regfft::brev(i, 5);
-    }
-}
 
 bool rows_mr_width(int W) { return W % 16 == 0 && regfft::mr_length(W / 16); }
 template <> bool rows_supported<float>(int W, int K) {
@@ -32,7 +24,7 @@ template <typename T> void rows_twiddles(int W, cx<T> *twA) {
     const double two_pi = 6.283185307179586476925286766559;
     for (int w = 0; w < NW; ++w)
         for (int i = 0; i < N1; ++i) {
-            const double ang = -two_pi * (double)(w * rows_rev(N1, i)) / (double)W;
+            const double ang = -two_pi * (double)(w * regfft::line_rev(N1, i)) / (double)W;
             twA[w * N1 + i] = mk<T>((T)std::cos(ang), (T)std::sin(ang));
         }
 }

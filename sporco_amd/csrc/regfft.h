@@ -160,7 +160,8 @@ constexpr double mr_sin(int num, int den) { return mr_cos(4 * num - den, 4 * den
 // The supported lengths (one list for the kernels' instantiations, the launchers' switches and the
 // host tables): X(n) for every n.  16 n = 160, 192, 224, 240, 288, 320, 336, 384, 400, 432, 448, 480.
 // The two halves are instantiated in translation units of their own (csc_rows_mr.hip /
-// csc_rows_mr2.hip, csc_pgm_mr.hip / csc_pgm_mr2.hip), which compile side by side.
+// csc_rows_mr2.hip, csc_pgm_mr.hip / csc_pgm_mr2.hip, csc_fused_mr.hip / csc_fused_mr2.hip), which
+// compile side by side.
 #define SA_MR_LENGTHS_LO(X) X(10) X(12) X(14) X(15) X(18) X(20)
 #define SA_MR_LENGTHS_HI(X) X(21) X(24) X(25) X(27) X(28) X(30)
 #define SA_MR_LENGTHS(X) SA_MR_LENGTHS_LO(X) SA_MR_LENGTHS_HI(X)
@@ -224,6 +225,15 @@ template <int N> constexpr int mr_pos(int k) {      // ... and the position that
     for (int i = 0; i < N; ++i)
         if (mr_rev<N>(i) == k) return i;
     return -1;
+}
+// ... at run time, for the host tables of a line shape's N1 (with_line_shape: a mixed-radix length, or 32)
+inline int line_rev(int N1, int i) {
+    switch (N1) {
+#define SA_MR_CASE(n) case n: return mr_rev<n>(i);
+    SA_MR_LENGTHS(SA_MR_CASE)
+#undef SA_MR_CASE
+    default: return brev(i, 5);
+    }
 }
 // one table for every in-register length: rev / pos of the power-of-two lengths are the bit reversal
 template <int N> constexpr int rev1(int i) {
