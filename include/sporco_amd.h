@@ -117,6 +117,8 @@ typedef struct {
 #define SPORCO_AMD_VAR_DMU0 22 /* real  (H,W,C,N,1) mask-decoupling D-step: block 0 of U           */
 #define SPORCO_AMD_VAR_WML 23  /* real  (H,W,C,N,K) ConvBPDNInhib: lateral inhibition weights (inhib_update) */
 #define SPORCO_AMD_VAR_WMS 24  /* real  (H,W,C,N,K) ConvBPDNInhib: self inhibition weights                  */
+#define SPORCO_AMD_VAR_TVY 25  /* real  (3,H,W,C,N,K) ConvBPDNScalarTV / VectorTV: the blocks (y_0, y_1, y_L) of Y */
+#define SPORCO_AMD_VAR_TVU 26  /* real  (3,H,W,C,N,K) ... and of U                                              */
 /* Dictionary-sized state of the D-step (pgm.ccmod.ConvCnstrMOD, admm.ccmod consensus Y =
  * DX): real (H,W,K) / complex (H,Wf,K).  Ids 19..31 are reserved. */
 #define SPORCO_AMD_VAR_DX 32      /* real  dictionary iterate X (zero-padded filters)    */
@@ -689,6 +691,51 @@ typedef struct {
  * slots of out are zero. */
 int sporco_amd_csc_inhib_update(sporco_amd_csc_t h, const sporco_amd_inhib_params *p,
                                 double out[SPORCO_AMD_OUT_COUNT]);
+
+/* ---- ADMM with total-variation terms: sporco.admm.cbpdntv.ConvBPDNScalarTV (cbpdntv.py:31-571)
+ * and ConvBPDNVectorTV (:577-727) ------------------------------------------------------------------
+ * The constraint is (Gamma_0; Gamma_1; I) x = (y_0; y_1; y_L) (:56-65): Y and U have three blocks,
+ * kept block after block in VAR_TVY / VAR_TVU.  The reference's gradient filters are the two-tap
+ * [1, -1] (signal.gradient_filters), so G_i x = x - (its circular predecessor along axis i) and
+ * G_i^T v = v - (its circular successor): the kernels below are stencils, not transforms.
+ *
+ * One iteration, driven by the caller:
+ *   1. sporco_amd_csc_tv_xstep, which is sporco_amd_csc_admm_xstep with SPORCO_AMD_FLAG_GRADREG |
+ *      SPORCO_AMD_FLAG_KEEP_X, params.mu = params.rho: the system (D^H D + rho Wtv^2 GHGf + rho) x = D^H s + rho A^T (Y - U) (:277-298)
+ *      is ConvBPDNGradReg's with the grad-weight array Wtv^2 (tv_setup sets it), and the handle's own
+ *      VAR_Y / VAR_U hold P = A^T Y and Q = A^T U (tv_adjoint writes them), so the x step's
+ *      rfftn(Y - u_scale U) is the reference's right-hand side.  LinSolveCheck: its FLAG_XRRS sums.
+ *   2. sporco_amd_csc_tv_ystep;  3. sporco_amd_csc_tv_adjoint.
+ *
+ * setup: tvw holds n = 1 (scalar TVWeight) or n = K weights (:213-218), doubles whatever the
+ * handle's dtype; vector_tv != 0 selects ConvBPDNVectorTV's norm.  Replaces the handle's
+ * grad-weight array.  VAR_TVY / VAR_TVU start at zero; after uploading a Y0 / U0 into them call
+ * tv_adjoint once.  Single-channel dictionaries, no volume handles. */
+int sporco_amd_csc_tv_setup(sporco_amd_csc_t h, const double *tvw, int32_t n, int32_t vector_tv);
+/* The x step of the TV classes on VAR_Y = A^T Y, VAR_U = A^T U: sporco_amd_csc_admm_xstep with
+ * FLAG_GRADREG | FLAG_KEEP_X and mu = rho (set here; params.mu is ignored) when every filter has the
+ * same TVWeight.  With different weights per filter the reference hands its diagonal to
+ * linalg.solvedbi_sm (cbpdntv.py:290-292), whose formula solves the system only for a diagonal that
+ * is constant along the filter axis; the reference's arithmetic is reproduced then (generic chain,
+ * profile slot "sm_solve"), and FLAG_XRRS reports the residual the reference's LinSolveCheck reports.
+ * out[DFID] (FLAG_OBJ without FLAG_FEVAL_Y) and out[XRRS_*] as sporco_amd_csc_admm_xstep. */
+int sporco_amd_csc_tv_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]);
+/* One launch (profile slot "tv_ystep") after the x step, reading X: relax_AX (:542-559) with
+ * AXnr = (Wtv G_0 x, Wtv G_1 x, x); Y_{0,1} = prox_l2(AX_{0,1} + U_{0,1}, mu / rho) over the two
+ * gradient components of a filter (:314-321) or, vector TV, over the components and all filters of a
+ * pixel of one channel and signal (:707-715); Y_L = prox_l1(AX_L + U_L, (lmbda / rho) wl1);
+ * U += AX - Y (admm.py:434-437).  Uses params.rho, lmbda, mu, rlx, u_scale (applied to VAR_TVU as it
+ * is read) and the flags GEVAL_Y, OBJ, FEVAL_Y.  out[R2] = sum (AXnr - Y)^2, out[AX2] = sum AXnr^2,
+ * out[Y2] = sum Y^2 over the three blocks (admm.py:722-775), out[L1] = sum |wl1 g_L|, out[L21] =
+ * sum sqrt(sum g_{0,1}^2) (obfn_reg, :439-446 / :719-727; g is Y with FLAG_GEVAL_Y, else AXnr), and
+ * with FLAG_OBJ | FLAG_FEVAL_Y out[DFID] at rfftn(y_L) (:325-331); the other slots are zero. */
+int sporco_amd_csc_tv_ystep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]);
+/* One launch (profile slot "tv_adjoint"): VAR_Y <- p = y_L + Wtv sum_i G_i^T y_i (cnst_AT, :470-520),
+ * VAR_U <- q = u_scale (the same of U); out[S2] = sum (p - previous VAR_Y)^2 -- the dual residual
+ * ||A^T (Y - Yprev)||^2 of admm.py:745-752 without its rho --, out[U2] = sum q^2 (:765-775). */
+int sporco_amd_csc_tv_adjoint(sporco_amd_csc_t h, double u_scale, double out[SPORCO_AMD_OUT_COUNT]);
 
 /* ---- online dictionary learning (sporco.dictlrn.onlinecdl.OnlineConvBPDNDictLearn.dstep,
  * onlinecdl.py:310-333) -------------------------------------------------------------------

@@ -19,6 +19,7 @@ VAR_CX, VAR_CU = 17, 18
 VAR_MY0, VAR_MU0 = 19, 20
 VAR_DMY0, VAR_DMU0 = 21, 22
 VAR_WML, VAR_WMS = 23, 24
+VAR_TVY, VAR_TVU = 25, 26
 VAR_DX, VAR_DXF, VAR_DYF, VAR_DXFPRV, VAR_DYFPRV = 32, 33, 34, 35, 36
 VAR_DVF, VAR_DGF, VAR_DT0, VAR_DT1, VAR_DT2 = 37, 38, 39, 40, 41
 VAR_DSX, VAR_DSU = 42, 43
@@ -81,6 +82,7 @@ EXPORTS = (
     'sporco_amd_csc_mdcpl_init', 'sporco_amd_csc_mdcpl_iter', 'sporco_amd_csc_dstep_md_init',
     'sporco_amd_csc_set_data_mask', 'sporco_amd_csc_masked_grad',
     'sporco_amd_csc_inhib_setup', 'sporco_amd_csc_inhib_update',
+    'sporco_amd_csc_tv_setup', 'sporco_amd_csc_tv_xstep', 'sporco_amd_csc_tv_ystep', 'sporco_amd_csc_tv_adjoint',
     'sporco_amd_csc_profile', 'sporco_amd_csc_profile_read', 'sporco_amd_profile_slots',
     'sporco_amd_dev_malloc', 'sporco_amd_dev_free', 'sporco_amd_dev_upload',
     'sporco_amd_dev_download', 'sporco_amd_dev_axpby', 'sporco_amd_tikhonov_filter_dev',
@@ -295,6 +297,10 @@ def load(path=None):
         'sporco_amd_csc_mdcpl_init': [vp, vp],
         'sporco_amd_csc_inhib_setup': [vp, dptr, i32, dptr, i32, dptr, i32, i32, dbl],
         'sporco_amd_csc_inhib_update': [vp, ctypes.POINTER(InhibParams), dptr],
+        'sporco_amd_csc_tv_setup': [vp, dptr, i32, i32],
+        'sporco_amd_csc_tv_xstep': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_tv_ystep': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_tv_adjoint': [vp, dbl, dptr],
         'sporco_amd_csc_mdcpl_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_dstep_init': [vp, vp],
         'sporco_amd_csc_dstep_md_init': [vp, vp, vp],
@@ -472,6 +478,8 @@ class Solver(object):
         if var in (VAR_CX, VAR_CU) and self.Cd > 1:
             # consensus copies of a multi-channel dictionary: one (Cd, K) block per image
             return (H, W, N, self.Cd, K), self.dtype
+        if var in (VAR_TVY, VAR_TVU):
+            return (3, H, W, C, N, K), self.dtype
         return (H, W, C, N, K), self.dtype
 
     # -- set-up -----------------------------------------------------------
@@ -696,6 +704,34 @@ class Solver(object):
         p = InhibParams(float(lmbda), float(mu), float(gamma), float(smooth), int(flags))
         out = self._out()
         check(self._lib.sporco_amd_csc_inhib_update(self._h, ctypes.byref(p), out))
+        return list(out)
+
+    def tv_setup(self, tvw, vector_tv):
+        """ConvBPDNScalarTV / ConvBPDNVectorTV state (sporco_amd_csc_tv_setup): ``tvw`` a scalar or
+        one weight per filter."""
+        w = np.ascontiguousarray(tvw, dtype=np.float64).ravel()
+        if w.size not in (1, self.dims[4]):
+            raise ValueError("TVWeight must be a scalar or hold one value per filter")
+        check(self._lib.sporco_amd_csc_tv_setup(
+            self._h, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), w.size, 1 if vector_tv else 0))
+
+    def tv_xstep(self, params):
+        """The x step of the TV classes (sporco_amd_csc_tv_xstep); returns the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_tv_xstep(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def tv_ystep(self, params):
+        """relax + y step + u step of the TV classes (sporco_amd_csc_tv_ystep); returns the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_tv_ystep(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def tv_adjoint(self, u_scale=1.0):
+        """P = A^T Y, Q = u_scale A^T U into VAR_Y / VAR_U (sporco_amd_csc_tv_adjoint); returns the
+        sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_tv_adjoint(self._h, float(u_scale), out))
         return list(out)
 
     def admm_iter_dev(self, params, out_dev_ptr):

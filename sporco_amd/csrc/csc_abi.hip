@@ -589,6 +589,46 @@ int sporco_amd_csc_inhib_update(sporco_amd_csc_t h, const sporco_amd_inhib_param
     SA_API_END
 }
 
+int sporco_amd_csc_tv_setup(sporco_amd_csc_t h, const double *tvw, int32_t n, int32_t vector_tv) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(tvw != nullptr, "null TVWeight");
+    h->impl->tv_setup(tvw, n, vector_tv != 0);
+    SA_API_END
+}
+
+int sporco_amd_csc_tv_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->tv_xstep(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
+int sporco_amd_csc_tv_ystep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->tv_ystep(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
+int sporco_amd_csc_tv_adjoint(sporco_amd_csc_t h, double u_scale, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->tv_adjoint(u_scale, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
 int sporco_amd_csc_dstep_init(sporco_amd_csc_t h, const void *Y0) {
     SA_API_BEGIN
     SA_HANDLE(h);

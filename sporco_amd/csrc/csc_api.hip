@@ -26,7 +26,7 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                            "admm_persist_run",
                                     "setcoef_rows",     "setcoef_cols",     "ccmod_grad_tiled",
                                     "fft_c2r_vpost",    "fft_c2r_vpost_emit",
-                                    "inhib_update"};
+                                    "inhib_update",     "tv_ystep",         "tv_adjoint"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -416,6 +416,7 @@ template <typename T> struct Csc : CscBase {
         (void)hipStreamSynchronize(st);
         place_release_spares();
         inhib_release();
+        tv_release();
         big_free(gemit);
         if (part_vpost) (void)hipFree(part_vpost);
         big_free(cols_out[0]);
@@ -464,6 +465,8 @@ template <typename T> struct Csc : CscBase {
                                        : sizeof(T) * (int64_t)H * W * KD();
         // (consensus copies of a multi-channel dictionary: one (Cd, K) block per image)
         if (var == SPORCO_AMD_VAR_CX || var == SPORCO_AMD_VAR_CU) return sizeof(T) * E * Cd;
+        // (the three blocks of the TV classes' Y and U, one after the other)
+        if (var == SPORCO_AMD_VAR_TVY || var == SPORCO_AMD_VAR_TVU) return sizeof(T) * E * 3;
         return var_is_complex(var) ? sizeof(cx<T>) * EF : sizeof(T) * E;
     }
 
@@ -601,6 +604,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_maskdcpl.inc"
 #include "api_dstep.inc"
 #include "api_inhib.inc"
+#include "api_tv.inc"
 };
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

@@ -19,6 +19,7 @@
 #include "csc_kernels.h"
 #include "csc_pgm.h"
 #include "csc_rows.h"
+#include "csc_tv.h"
 #include "fft.h"
 
 #include <atomic>
@@ -86,6 +87,8 @@ enum ProfSlot {
     PS_C2R_VPOST,               // generic chain: c2r row pass + epilogue of the single-array state in one
     PS_C2R_VPOST_EMIT,          // kernel (fft.h fft_c2r_vpost), ... + the next iteration's row spectrum
     PS_INHIB,                   // ConvBPDNInhib: the inhibition-weight update (csc_inhib.h)
+    PS_TV_YSTEP,                // ConvBPDNScalarTV / VectorTV: relax + y step + u step + sums (csc_tv.h)
+    PS_TV_ADJOINT,              // ... and P = A^T Y, Q = A^T U with the dual-residual sums
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -217,6 +220,10 @@ struct CscBase {
     virtual void inhib_setup(const double *Wg, int Ng, const double *taps_h, int nth, const double *taps_w,
                              int ntw, bool want_self, double lmbda) = 0;
     virtual void inhib_update(const sporco_amd_inhib_params &p, double *out_dev) = 0;
+    virtual void tv_setup(const double *tvw, int n, bool vector_tv) = 0;
+    virtual void tv_xstep(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void tv_ystep(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void tv_adjoint(double u_scale, double *out_dev) = 0;
     virtual void read_out(const double *out_dev, double *out_host) = 0;
     double *out_dev_default = nullptr;
     Profiler prof;
@@ -259,7 +266,7 @@ static bool var_is_dict_sized(int var) {
 }
 
 static bool var_is_valid(int var) {
-    return (var >= 0 && var <= SPORCO_AMD_VAR_WMS) ||
+    return (var >= 0 && var <= SPORCO_AMD_VAR_TVU) ||
            (var >= SPORCO_AMD_VAR_DX && var < SPORCO_AMD_VAR_COUNT);
 }
 
