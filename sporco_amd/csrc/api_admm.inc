@@ -239,6 +239,14 @@
                !(p.flags & (F_NOBNDRY | F_AMS | F_KEEP_X | F_GRADREG));
     }
 
+    // The generic chain's iterate after an iteration with the parameters p: live, it is V in the
+    // buffer of vars[U] (no buffer of its own in the record, no previous V); the threshold and
+    // NonNegCoef are kept either way, for the next iteration's choice
+    void commit_generic_v(const sporco_amd_admm_params &p, bool live) {
+        it.form = live ? IterForm::GenericV : IterForm::YU;
+        it.cur = held_v(p, nullptr, (T)(p.lmbda / p.rho), T(0));
+    }
+
     void admm_iter(const sporco_amd_admm_params &p, double *out_dev) override {
         SA_REQUIRE(depth == 1 || !(p.flags & (F_NOBNDRY | F_GRADREG | F_AMS)),
                    "volume handle: no NoBndryCross, gradient term or AddMaskSim (their kernels know two axes)");
@@ -258,7 +266,7 @@
         // buffer of U) and the row transform and the next epilogue derive (Y, U) from it:
         // thirteen passes over an array of the coefficients' size instead of sixteen.
         const bool gnn = p.flags & F_NONNEG;
-        const bool gv_in = gv_live && gvform_ok(p) && gv_nonneg == gnn;
+        const bool gv_in = it.form == IterForm::GenericV && gvform_ok(p) && it.cur.nonneg == gnn;
         const bool gv_out = gvform_ok(p) && (gv_in || touch_epoch == gen_epoch);
         // (float64: measured +5 ... 7 % there -- 256 x 256, K = 32: 2107 -> 2217 it/s --, -2 ... +3 % in
         // float32, whose three separate kernels are not bound by the passes it saves:
@@ -277,17 +285,15 @@
         }
         T *const ybuf = gv_in ? static_cast<T *>(vars[SPORCO_AMD_VAR_Y]) : rv(SPORCO_AMD_VAR_Y);
         T *const ubuf = gv_in ? static_cast<T *>(vars[SPORCO_AMD_VAR_U]) : rv(SPORCO_AMD_VAR_U);
-        xstep_impl(p, out_dev, gv_in ? ubuf : nullptr, gv_thr);
+        xstep_impl(p, out_dev, gv_in ? ubuf : nullptr, it.cur.thr);
         PostParams<T> pp;
         pp.x = rv(SPORCO_AMD_VAR_X);
         pp.y = ybuf;
         pp.u = ubuf;
         pp.v_in = gv_in ? ubuf : nullptr;
         pp.v_out = gv_out ? ubuf : nullptr;
-        pp.thr_prev = gv_thr;
-        gv_live = gv_out;
-        gv_nonneg = gnn;
-        gv_thr = (T)(p.lmbda / p.rho);
+        pp.thr_prev = it.cur.thr;
+        commit_generic_v(p, gv_out);
         pp.rlx = (T)p.rlx;
         pp.thr = (T)(p.lmbda / p.rho);
         pp.thr21 = (T)(p.mu / p.rho);
@@ -330,7 +336,7 @@
         T *const vbuf = static_cast<T *>(vars[SPORCO_AMD_VAR_U]);
         cx<T> *Xf = cv(SPORCO_AMD_VAR_XF);
         if (!(t_ready && p.u_scale == 1.0)) {
-            const VformIn<T> vfi{gv_thr, (bool)(p.flags & F_NONNEG)};
+            const VformIn<T> vfi{it.cur.thr, (bool)(p.flags & F_NONNEG)};
             ProfScope ps(prof, PS_FFT_R2C);
             fft_r2c<T>(st, planW, vbuf, nullptr, (T)p.u_scale, Xf, H, P, (int64_t)W * P, P, (int64_t)Wf * P, P,
                        0, 0, 0, &vfi);
@@ -366,7 +372,7 @@
         pp.y = pp.u = nullptr;
         pp.v_in = vbuf;
         pp.v_out = vbuf;
-        pp.thr_prev = gv_thr;
+        pp.thr_prev = it.cur.thr;
         pp.rlx = (T)p.rlx;
         pp.thr = (T)(p.lmbda / p.rho);
         pp.thr21 = T(0);
@@ -385,9 +391,7 @@
                               SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1, SPORCO_AMD_OUT_L21};
         const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
         finalize(part_vpost, (int)nb, 8, 7, slots, scales, out_dev);
-        gv_live = true;
-        gv_nonneg = p.flags & F_NONNEG;
-        gv_thr = (T)(p.lmbda / p.rho);
+        commit_generic_v(p, true);
         // X of this iteration: one c2r row pass of the column pass's output away
         x_invalid = p.flags & F_NO_X;
         md_x_pending = !x_invalid;

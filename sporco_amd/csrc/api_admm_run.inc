@@ -21,62 +21,20 @@
                admm_persist_supported<T>(H, W, K) && !wl1.ptr && c.max_iter >= 3 &&
                !(p.flags & (F_NOBNDRY | F_AMS | F_JOINT)) && admm_persist_resident<T>(H, W, K, CN);
     }
-    PersistIterArgs<T> persist_iter_args(const sporco_amd_admm_params &p, const T *vin, T *vout,
+    // (V form in and out, always emitting; every iteration-dependent scalar from the control block)
+    PersistIterArgs<T> persist_iter_args(const sporco_amd_admm_params &p, T *vin, T *vout,
                                          double *prow, double *pcol) {
         PersistIterArgs<T> a;
-        cx<T> *Xf = cv(SPORCO_AMD_VAR_XF);
-        a.fwd.y = a.fwd.u = nullptr;
-        a.fwd.v = vin;
-        a.fwd.flags = p.flags;
-        a.fwd.C = C;
-        a.fwd.N = N;
-        a.fwd.dH = p.dH;
-        a.fwd.dW = p.dW;
+        a.fwd = rows_fwd_args(held_v(p, vin, T(0), T(0)), p);
         a.fwd.s2 = T(1);
-        a.fwd.t = Xf;
-        a.fwd.Ks = Ks;
-        a.fwd.twA = twRows;
-        a.fwd.H = H;
-        a.fwd.W = W;
-        a.fwd.CN = CN;
-        a.fwd.K = K;
-        a.fwd.P = P;
-        a.cols.t = Xf;
-        a.cols.dft = dft;
-        a.cols.sft = sft;
-        a.cols.gramt = gramt;
-        a.cols.twA = twA;
-        a.cols.twB = twB;
-        a.cols.rho = (T)p.rho;
-        a.cols.H = H;
-        a.cols.W = W;
-        a.cols.CN = CN;
-        a.cols.K = K;
+        a.cols = fused_cols_args(p.rho);
         a.cols.partials = pcol;
-        a.cols.Ks = Ks;
-        a.post.twA = twRows;
-        a.post.t_next = Xf;
-        a.post.t = Xf;
-        a.post.twW = planW.tw<T>();
-        a.post.y = a.post.u = nullptr;
-        a.post.y_out = a.post.u_out = nullptr;
+        a.post = rows_post_args(p);
+        a.post.t_next = a.fwd.t;
         a.post.v_in = vin;
         a.post.v_out = vout;
-        a.post.x = nullptr;
-        a.post.scale = T(1.0 / ((double)H * (double)W));
-        a.post.rlx = (T)p.rlx;
-        a.post.thr = T(0);
+        a.post.thr = T(0);      // (thr and u_scale: the control block's)
         a.post.u_scale = T(1);
-        a.post.flags = p.flags;
-        a.post.H = H;
-        a.post.W = W;
-        a.post.C = C;
-        a.post.N = N;
-        a.post.K = K;
-        a.post.dH = p.dH;
-        a.post.dW = p.dW;
-        a.post.P = P;
-        a.post.Ks = Ks;
         a.post.partials = prow;
         return a;
     }
@@ -135,61 +93,24 @@
     // one iteration of admm_iter_fused with every iteration-dependent scalar taken from ctl_dev
     // vout set: the single-array state of csc_rows.h -- the iterate is read from vin (null: from
     // (Y, U), the first iteration of such a run) and V' is written to vout
-    int64_t enqueue_iter_ctl(const sporco_amd_admm_params &p, const T *vin = nullptr,
-                             T *vout = nullptr) {
+    int64_t enqueue_iter_ctl(const sporco_amd_admm_params &p, T *vin = nullptr, T *vout = nullptr) {
         T *Y = vin ? nullptr : static_cast<T *>(vars[SPORCO_AMD_VAR_Y]);
         T *U = vin ? nullptr : static_cast<T *>(vars[SPORCO_AMD_VAR_U]);
-        cx<T> *Xf = cv(SPORCO_AMD_VAR_XF);
+        const bool striped = cols_striped() && !fused_slabs;
         {
-            RowsFwdArgs<T> ra;
+            // (thresholds of a V input: the control block's)
+            auto ra = vin ? rows_fwd_args(held_v(p, vin, T(0), T(0)), p) : rows_fwd_args();
             ra.y = Y;
             ra.u = U;
-            ra.v = vin;
-            ra.flags = p.flags;
-            ra.C = C;
-            ra.N = N;
-            if (vin) {
-                ra.wl1 = wl1;
-                ra.dH = p.dH;
-                ra.dW = p.dW;
-                ra.ams_bits = ams_bits_of(p);
-                ra.ams_k = Ku - 1;
-            }
             ra.s2 = T(1);
-            ra.t = Xf;
-            ra.Ks = Ks;
-            ra.twA = twRows;
-            ra.H = H;
-            ra.W = W;
-            ra.CN = CN;
-            ra.K = K;
-            ra.P = P;
             ra.ctl = ctl_dev;
-            ProfScope ps(prof, vin ? PS_ROWS_FWD_V : PS_ROWS_FWD);
-            launch_rows_fwd<T>(st, ra);
+            run_rows_fwd(ra);
         }
         {
-            FusedColsArgs<T> fa;
-            fa.t = Xf;
-            fa.dft = dft;
-            fa.sft = sft;
-            fa.gramt = gramt;
-            fa.twA = twA;
-            fa.twB = twB;
-            fa.rho = (T)p.rho;
-            fa.H = H;
-            fa.W = W;
-            fa.CN = CN;
-            fa.K = K;
-            fa.partials = part_f;
-            fa.Ks = Ks;
+            auto fa = fused_cols_args(p.rho, striped);
             fa.ctl = ctl_dev;
-            if (cols_striped() && !fused_slabs) {
-                fa.out_even = cols_out[0];
-                fa.out_odd = cols_out[1];
-            }
             ProfScope ps(prof, PS_FUSED_COLS);
-            if (fused_slabs) {      // 64 < K <= 256: the two slab kernels (csc_fused.h)
+            if (fused_slabs) {      // 64 < K <= 256: cooperating slab workgroups (csc_fused.h)
                 FusedSlabArgs<T> sa;
                 sa.c = fa;
                 sa.qpart = qpart;
@@ -199,55 +120,28 @@
             }
             xf_tiled = true;
         }
-        RowsPostArgs<T> pa;
-        pa.twA = twRows;
-        pa.t_next = nullptr;     // plain variant first, then the emitting one: ctl->emit picks
-        pa.t = Xf;
-        if (cols_striped() && !fused_slabs) {
-            pa.t = cols_out[0];
-            pa.t_odd = cols_out[1];
-        }
-        pa.twW = planW.tw<T>();
+        auto pa = rows_post_args(p, striped);
         pa.y = Y;
         pa.u = U;
         pa.y_out = y_alt;
         pa.u_out = u_alt;
         pa.v_in = vin;
         pa.v_out = vout;
-        pa.x = nullptr;
-        pa.scale = T(1.0 / ((double)H * (double)W));
-        pa.rlx = (T)p.rlx;
-        pa.thr = T(0);
+        pa.thr = T(0);          // (thr, u_scale and the previous thresholds: the control block's)
         pa.u_scale = T(1);
-        pa.flags = p.flags;
-        pa.H = H;
-        pa.W = W;
-        pa.C = C;
-        pa.N = N;
-        pa.K = K;
-        pa.dH = p.dH;
-        pa.dW = p.dW;
-        pa.P = P;
-        pa.wl1 = wl1;
-        pa.Ks = Ks;
-        pa.ams_bits = ams_bits_of(p);
-        pa.ams_k = Ku - 1;
-        pa.partials = part_rows;
         pa.ctl = ctl_dev;
+        // plain variant first, then the emitting one: ctl->emit picks
         int64_t nt = 0;
         if (!run_always_emit) {
             ProfScope ps(prof, vin ? PS_ROWS_INV_POST_V : PS_ROWS_INV_POST);
             nt = launch_rows_inv_post<T>(st, pa);
         }
-        pa.t_next = Xf;
+        pa.t_next = cv(SPORCO_AMD_VAR_XF);
         {
             ProfScope ps(prof, vin ? PS_ROWS_INV_POST_V_EMIT : PS_ROWS_INV_POST_EMIT);
             nt = launch_rows_inv_post<T>(st, pa);
         }
-        if (!vout) {
-            std::swap(vars[SPORCO_AMD_VAR_Y], reinterpret_cast<void *&>(y_alt));
-            std::swap(vars[SPORCO_AMD_VAR_U], reinterpret_cast<void *&>(u_alt));
-        }
+        if (!vout) swap_alt_pair();
         return nt;
     }
 
@@ -256,7 +150,6 @@
                  sporco_amd_reduce_fn reduce, void *user) override {
         require_ready();
         if (!admm_run_supported(p)) return -1;
-        if (gv_live) ensure_yu();
         SA_REQUIRE(c.max_iter >= 0, "max_iter must not be negative");
         if (c.max_iter == 0) {
             *rho_out = p.rho;
@@ -268,13 +161,8 @@
         // V' = AX + U alone, rows_fwd and the next epilogue derive (Y, U) from it.  A run of a
         // few iterations (a dictionary-learning X-step) stays in the (Y, U) form: it would pay
         // the conversion back at once.
-        const bool nn = p.flags & F_NONNEG, jn = p.flags & F_JOINT;
-        if (v_live && (!vform_ok(p) || !vform_same_opts(p))) ensure_yu();
-        const bool vf = vform_ok(p) && (v_live || c.max_iter >= 4 || hint_vform);
-        if (!vf) ensure_yu();
-        const bool v_at_entry = v_live;
-        T *const v_entry = v_cur;
-        const T v_entry_thr = v_thr, v_entry_thr21 = v_thr21;
+        const VRoute vr = enter_iteration(p, c.max_iter >= 4 || hint_vform);
+        const bool vf = vr.out != nullptr;
         if (!ctl_dev) SA_HIP(hipMalloc((void **)&ctl_dev, sizeof(AdmmCtl)));
         if (rec_cap < c.max_iter) {
             if (rec_ring) SA_HIP(hipHostFree(rec_ring));
@@ -305,8 +193,8 @@
         in.autoscaling = c.auto_scaling;
         in.stdres = c.std_residuals;
         in.need_resid = c.need_residuals;
-        in.thr_prev = v_at_entry ? (float)v_entry_thr : 0.f;
-        in.thr21_prev = v_at_entry ? (float)v_entry_thr21 : 0.f;
+        in.thr_prev = (float)vr.in.thr;        // (zero when the run starts from (Y, U))
+        in.thr21_prev = (float)vr.in.thr21;
         in.no_speculation = sw.no_speculation ? 1 : 0;
         // Small problems (kernels of a few microseconds): the emitting epilogue always, and its
         // plain twin is not enqueued at all -- a wasted emit costs less than a launch that
@@ -334,26 +222,14 @@
                 ++done;
             }
         };
-        T *vb_in = v_at_entry ? v_entry : nullptr;     // V form: input of the next enqueued iteration
-        T *const vb_first = vf ? (vb_in == y_alt ? u_alt : y_alt) : nullptr;   // output of the first
+        T *vb_in = vr.in.buf;     // V form: input of the next enqueued iteration
         auto enqueue_one = [&]() {
-            T *vb_out = vf ? (vb_in == y_alt ? u_alt : y_alt) : nullptr;
+            T *vb_out = vf ? other_alt(vb_in) : nullptr;
             const int64_t nt = enqueue_iter_ctl(p, vb_in, vb_out);
             vb_in = vb_out;
             if (want_sums) {
-                const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                                      SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1,
-                                      SPORCO_AMD_OUT_L21};
-                const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
-                const int fslots[2] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_RGR};
-                const double fscales[2] = {1.0 / ((double)H * W), 1.0 / ((double)H * W)};
-                const bool dfid = p.flags & F_OBJ;
-                {
-                    ProfScope ps(prof, PS_FINALIZE);
-                    launch_finalize2(st, part_rows, (int)nt, 8, (p.flags & F_JOINT) ? 7 : 6, slots,
-                                     scales, part_f, part_f_rows,
-                                     1, dfid ? 1 : 0, fslots, fscales, out_dev);
-                }
+                // (no gradient term, data fidelity at X: admm_run_supported)
+                finalize_iter_sums(p, nt, out_dev);
                 if (reduce) reduce(user, out_dev);
                 else if (comm_user) comm_reduce_sums(comm_user, out_dev, st);
             }
@@ -373,7 +249,7 @@
             // small problem: the first iteration as usual (it enters the single-array state),
             // every further one inside one launch
             enqueue_one();
-            T *v0 = vb_in, *v1 = (v0 == y_alt) ? u_alt : y_alt;
+            T *v0 = vb_in, *v1 = other_alt(v0);
             enq += run_persist(p, 1, c.max_iter, v0, v1, want_sums);
             if (c.need_residuals) poll(enq, false);
         }
@@ -392,37 +268,21 @@
         sync();
         poll(enq, false);
         const int n = stop_at >= 0 ? stop_at + 1 : enq;
-        // launches enqueued after the stopping iteration did nothing: undo their buffer swaps
-        if (!vf && ((enq - n) & 1)) {
-            std::swap(vars[SPORCO_AMD_VAR_Y], reinterpret_cast<void *&>(y_alt));
-            std::swap(vars[SPORCO_AMD_VAR_U], reinterpret_cast<void *&>(u_alt));
-        }
         if (vf) {
-            // iteration j wrote its V' to vb_first (j even) or to the other alt buffer (j odd);
+            // iteration j wrote its V' to vr.out (j even) or to the other alt buffer (j odd);
             // thresholds as the control block formed them: (float)(lambda / rho of the iteration)
-            T *other_first = vb_first == y_alt ? u_alt : y_alt;
-            v_cur = ((n - 1) & 1) ? other_first : vb_first;
-            v_thr = (T)(p.lmbda / rec_ring[n - 1].rho);
-            v_thr21 = (T)(p.mu / rec_ring[n - 1].rho);
-            if (n >= 2) {
-                v_prev_kind = 2;
-                v_prev_thr = (T)(p.lmbda / rec_ring[n - 2].rho);
-                v_prev_thr21 = (T)(p.mu / rec_ring[n - 2].rho);
-            } else if (v_at_entry) {
-                v_prev_kind = 2;
-                v_prev_thr = v_entry_thr;
-                v_prev_thr21 = v_entry_thr21;
-            } else {
-                v_prev_kind = 1;
-            }
-            v_nonneg = nn;
-            v_joint = jn;
-            v_opts = p.flags & (F_NOBNDRY | F_AMS);
-            v_dH = p.dH;
-            v_dW = p.dW;
-            v_live = true;
+            auto held = [&](int j) {
+                return held_v(p, (j & 1) ? other_alt(vr.out) : vr.out, (T)(p.lmbda / rec_ring[j].rho),
+                              (T)(p.mu / rec_ring[j].rho));
+            };
+            const HeldV cur = held(n - 1), before = n >= 2 ? held(n - 2) : vr.in;
+            commit_v(p, cur, before.buf ? &before : nullptr);
+        } else {
+            // launches enqueued after the stopping iteration did nothing: undo their buffer swaps --
+            // and that of iteration n - 1, which commit_yu() makes
+            if ((enq - n + 1) & 1) swap_alt_pair();
+            commit_yu(p);
         }
-        vp_pending = false;
         AdmmCtl fin;
         SA_HIP(hipMemcpy(&fin, ctl_dev, sizeof(AdmmCtl), hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i) {
@@ -445,70 +305,23 @@
         stable_run = fin.stable_run > 0 ? fin.stable_run - 1 : 0;   // (admm_iter_fused re-derives it)
         if (fin.u_scale != 1.0) stable_run = 0;
         t_ready = fin.emitted != 0;
-        last_p = p;
-        last_p.rho = rec_ring[n - 1].rho;
+        last_p.rho = rec_ring[n - 1].rho;      // (the commit above took the rest from p)
         last_p.u_scale = rec_ring[n - 1].u_scale;
-        x_stale = true;
-        x_invalid = p.flags & F_NO_X;
-        prev_in_alt = !vf;
         return n;
     }
 
     // X = irfft_W(tile-major spectrum in the Xf buffer) / (H W): the row pass of
     // rows_inv_prox_fwd with a zero threshold (soft(v, 0) = v) and no forward half
     void rows_inverse_to(T *Xout, const cx<T> *t_in = nullptr) {
-        RowsProxArgs<T> ra;
+        auto ra = rows_prox_args();
         ra.t_in = t_in ? t_in : cv(SPORCO_AMD_VAR_XF);
         ra.Ks = t_in ? 0 : Ks;
         ra.t_out = nullptr;
         ra.x = Xout;
-        ra.twA = twRows;
-        ra.twW = planW.tw<T>();
-        ra.scale = T(1.0 / ((double)H * (double)W));
         ra.thr = T(0);
         ra.flags = 0;
-        ra.H = H;
-        ra.W = W;
-        ra.C = C;
-        ra.N = N;
-        ra.K = K;
         ra.dH = 1;
         ra.dW = 1;
-        ra.P = P;
-        ra.wl1 = Weight<T>();
-        ra.partials = part_rows;
         ProfScope ps(prof, PS_FFT_C2R);
         launch_rows_inv_prox_fwd<T>(st, ra);
-    }
-
-    void launch_rows_fwd_on(const T *Yin, const T *Uin, T s2, const T *Vin = nullptr,
-                            T thr_prev = T(0), uint32_t flags = 0, T thr21_prev = T(0),
-                            const sporco_amd_admm_params *vp = nullptr, cx<T> *t_out = nullptr) {
-        RowsFwdArgs<T> ra;
-        if (Vin && vp) {     // the options the derivation of Y from V repeats
-            ra.wl1 = wl1;
-            ra.dH = vp->dH;
-            ra.dW = vp->dW;
-            ra.ams_bits = ams_bits_of(*vp);
-            ra.ams_k = Ku - 1;
-        }
-        ra.y = Yin;
-        ra.u = Uin;
-        ra.v = Vin;
-        ra.thr_prev = thr_prev;
-        ra.thr21_prev = thr21_prev;
-        ra.flags = flags;
-        ra.C = C;
-        ra.N = N;
-        ra.s2 = s2;
-        ra.t = t_out ? t_out : cv(SPORCO_AMD_VAR_XF);
-        ra.Ks = Ks;
-        ra.twA = twRows;
-        ra.H = H;
-        ra.W = W;
-        ra.CN = CN;
-        ra.K = K;
-        ra.P = P;
-        ProfScope ps(prof, Vin ? PS_ROWS_FWD_V : PS_ROWS_FWD);
-        launch_rows_fwd<T>(st, ra);
     }

@@ -325,35 +325,16 @@
                 launch_gram_rows<T>(st, Zf, gramz_t, npix * CN, K);
                 gramz_valid = true;
             }
-            RowsFwdArgs<T> ra;
+            auto ra = rows_fwd_args(cns_f);
             ra.y = Y;
             ra.u = U;
             ra.s2 = (T)p.u_scale;
-            ra.t = cns_f;
-            ra.twA = twRows;
-            ra.H = H;
-            ra.W = W;
-            ra.CN = CN;
-            ra.K = K;
-            ra.P = P;
             ra.y_bcast = 1;
-            {
-                ProfScope ps(prof, PS_ROWS_FWD);
-                launch_rows_fwd<T>(st, ra);
-            }
-            FusedColsArgs<T> fa;
-            fa.t = cns_f;
+            run_rows_fwd(ra);
+            // (the coefficient spectra of each tile in the dictionary's place, their gram per tile)
+            auto fa = fused_cols_args(p.rho, false, cns_f);
             fa.dft = Zf;
-            fa.sft = sft;
             fa.gramt = gramz_t;
-            fa.twA = twA;
-            fa.twB = twB;
-            fa.rho = (T)p.rho;
-            fa.H = H;
-            fa.W = W;
-            fa.CN = CN;
-            fa.K = K;
-            fa.partials = part_f;
             fa.per_tile = 1;
             int64_t ntl;
             {

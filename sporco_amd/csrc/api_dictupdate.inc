@@ -28,39 +28,20 @@
         if (rows_ok && (cols256 || mr) && (fused || (fused_slabs && !cns_active && !mr)) &&
             !(cns_active && !cns_fused()) && !eq_active) {
             // rows then columns, register-resident, straight into the tile-major layout
-            RowsFwdArgs<T> ra;
             // (the iterate in its single-array form: Y = prox(V) is derived inside the row pass
-            // -- with s2 = 0 the kernel transforms Y - 0 U = Y -- instead of being written out first)
-            const bool from_v = var == SPORCO_AMD_VAR_Y && v_live;
+            // -- with s2 = 0 the kernel transforms Y - 0 U = Y -- instead of being written out first,
+            // under the options the iterate was produced with)
+            const bool from_v = var == SPORCO_AMD_VAR_Y && it.form == IterForm::FusedV;
+            cx<T> *Zf = cv(SPORCO_AMD_VAR_ZF);
+            auto ra = rows_fwd_args(Zf);
             if (from_v) {
-                ra.y = nullptr;
-                ra.v = v_cur;
-                ra.thr_prev = v_thr;
-                ra.thr21_prev = v_thr21;
-                ra.flags = (v_nonneg ? F_NONNEG : 0u) | (v_joint ? F_JOINT : 0u) | v_opts;
-                ra.C = C;
-                ra.N = N;
-                ra.wl1 = wl1;
-                ra.dH = v_dH;
-                ra.dW = v_dW;
-                if (v_opts & F_AMS) {
-                    sporco_amd_admm_params q = last_p;
-                    q.flags |= F_AMS;
-                    ra.ams_bits = ams_bits_of(q);
-                    ra.ams_k = Ku - 1;
-                }
+                sporco_amd_admm_params q = last_p;
+                q.flags = it.cur.flags();
+                ra = rows_fwd_args(it.cur, q, Zf);
             } else {
                 ra.y = rv(var);
             }
-            ra.u = nullptr;
             ra.s2 = T(0);
-            ra.t = cv(SPORCO_AMD_VAR_ZF);
-            ra.twA = twRows;
-            ra.H = H;
-            ra.W = W;
-            ra.CN = CN;
-            ra.K = K;
-            ra.P = P;
             {
                 ProfScope ps(prof, PS_SETCOEF_ROWS);
                 launch_rows_fwd<T>(st, ra);

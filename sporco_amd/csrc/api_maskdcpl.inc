@@ -38,8 +38,6 @@
         const T us = (T)p.u_scale;
         T *Y1 = rv(SPORCO_AMD_VAR_Y), *U1 = rv(SPORCO_AMD_VAR_U), *X = rv(SPORCO_AMD_VAR_X);
         T *Y0 = rv(SPORCO_AMD_VAR_MY0), *U0 = rv(SPORCO_AMD_VAR_MU0);
-        cx<T> *Xf = cv(SPORCO_AMD_VAR_XF);
-        (void)X;
         if (!md_sft) {
             SA_HIP(hipMalloc((void **)&md_sft, sizeof(cx<T>) * nsf));
             SA_HIP(hipMalloc((void **)&md_coef, sizeof(cx<T>) * nsf));
@@ -55,20 +53,9 @@
         }
         launch_rows_fwd_on(Y1, U1, us);
         t_ready = false;
-        FusedColsArgs<T> fa;
-        fa.t = Xf;
-        fa.dft = dft;
+        // (the system with rho = 1 and the spectrum of block 0 in Sf's place; its multipliers kept)
+        auto fa = fused_cols_args(1.0);
         fa.sft = md_sft;
-        fa.gramt = gramt;
-        fa.twA = twA;
-        fa.twB = twB;
-        fa.rho = T(1);
-        fa.H = H;
-        fa.W = W;
-        fa.CN = CN;
-        fa.K = K;
-        fa.Ks = Ks;
-        fa.partials = part_f;
         fa.coef_out = md_coef;
         {
             ProfScope ps(prof, PS_FUSED_COLS);
@@ -83,43 +70,21 @@
         }
         inv2(innerb, innerb, sreal, CNs);
         // block 1 through the row epilogue, in place ((Y, U) form), X kept for its readers
-        RowsPostArgs<T> pa;
         // with residuals wanted, the epilogue also leaves the row spectra of the NEW u1 in the
         // scratch spectrum (it has them in registers): the dual residual's input, for one write
         // pass instead of a row pass of its own over u1
         const bool want_dual = p.flags & F_RESID;
         cx<T> *wk = want_dual ? work_buf() : nullptr;
-        pa.twA = twRows;
+        auto pa = rows_post_args(p);
         pa.t_next = wk;
         pa.emit_u = want_dual ? 1 : 0;
-        pa.t = Xf;
-        pa.twW = planW.tw<T>();
         pa.y = Y1;
         pa.u = U1;
         pa.y_out = Y1;
         pa.u_out = U1;
-        pa.v_in = nullptr;
-        pa.v_out = nullptr;
         pa.x = (p.flags & F_KEEP_X) ? X : nullptr;
-        pa.scale = T(1.0 / ((double)H * (double)W));
-        pa.rlx = (T)p.rlx;
         pa.thr = (T)(p.lmbda / p.rho);
-        pa.thr21 = T(0);
         pa.u_scale = us;
-        pa.flags = p.flags;
-        pa.H = H;
-        pa.W = W;
-        pa.C = C;
-        pa.N = N;
-        pa.K = K;
-        pa.dH = p.dH;
-        pa.dW = p.dW;
-        pa.P = P;
-        pa.wl1 = wl1;
-        pa.Ks = Ks;
-        pa.ams_bits = nullptr;
-        pa.ams_k = Ku - 1;
-        pa.partials = part_rows;
         int64_t nt;
         {
             ProfScope ps(prof, PS_ROWS_INV_POST);
@@ -167,18 +132,8 @@
                 launch_permute_ab<cx<T>>(st, innerb, md_coef, H, (int64_t)Wf * CN, 1);
             }
             // (column FFT of those row spectra and the sum in one read pass: csc_fused.h)
-            FusedColsArgs<T> da;
-            da.t = wk;
-            da.dft = dft;
+            auto da = fused_cols_args(p.rho, false, wk);
             da.sft = md_coef;
-            da.twA = twA;
-            da.twB = twB;
-            da.H = H;
-            da.W = W;
-            da.CN = CN;
-            da.K = K;
-            da.Ks = Ks;
-            da.partials = part_f;
             {
                 ProfScope ps(prof, PS_SETCOEF_COLS);
                 nb = (int)launch_cols_dualres<T>(st, da);

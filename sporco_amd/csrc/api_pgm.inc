@@ -4,25 +4,15 @@
     // rows pass of the fused iteration: X = prox(irfft_W(t_in)), t_out = rfft_W(X)
     void pgm_rows_prox(const sporco_amd_pgm_params &p, const cx<T> *t_in, cx<T> *t_out, T *x,
                        double *out_dev) {
-        RowsProxArgs<T> ra;
+        auto ra = rows_prox_args();
         ra.t_in = t_in;
         ra.t_out = t_out;
         ra.x = x;
-        ra.twA = twRows;
-        ra.twW = planW.tw<T>();
-        ra.scale = T(1.0 / ((double)H * (double)W));
         ra.thr = (T)(p.lmbda / p.L);
         ra.flags = p.flags;
-        ra.H = H;
-        ra.W = W;
-        ra.C = C;
-        ra.N = N;
-        ra.K = K;
         ra.dH = p.dH;
         ra.dW = p.dW;
-        ra.P = P;
         ra.wl1 = wl1;
-        ra.partials = part_rows;
         int64_t nt;
         {
             ProfScope ps(prof, PS_PGM_ROWS_PROX);

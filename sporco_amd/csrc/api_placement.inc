@@ -34,7 +34,6 @@
     // directions -- bench.py `roofline.per_direction_ms` -- and a search that insists on 1.085 spends
     // its whole candidate budget without finding better).
     static constexpr double kPlaceClear = 1.05;
-    static constexpr double kPlaceClearReport = 1.05;
     static constexpr int kPlaceMaxCandidates = 12;                 // per decision, and at most
     static constexpr size_t kPlaceMaxBytes = (size_t)24 << 30;     // ... this much candidate memory
     static constexpr size_t kPlaceMaxArray = (size_t)4 << 30;      // arrays beyond this: placed as they come
@@ -230,7 +229,7 @@
                           "%s{\"role\": \"%s\", \"bytes\": %zu, \"candidates\": %d, \"same_region_GBps\": %.0f, "
                           "\"first_ratio\": %.3f, \"chosen_ratio\": %.3f, \"clear\": %s, \"ms\": %.1f}",
                           i ? ", " : "", r.role, r.bytes, r.tried, r.ref_gbps, r.first_ratio, r.chosen_ratio,
-                          r.chosen_ratio >= kPlaceClearReport ? "true" : "false", r.ms);
+                          r.chosen_ratio >= kPlaceClear ? "true" : "false", r.ms);
             out += buf;
         }
         return out + "]";

@@ -218,15 +218,13 @@
     }
     void download(int var, void *dst) override {
         if (var == SPORCO_AMD_VAR_YPREV || var == SPORCO_AMD_VAR_AX) ensure_prev_yu();
-        if (prev_in_alt && y_alt && (var == SPORCO_AMD_VAR_YPREV || var == SPORCO_AMD_VAR_AX)) {
+        if (it.prev_at == PrevAt::AltYU && y_alt && (var == SPORCO_AMD_VAR_YPREV || var == SPORCO_AMD_VAR_AX)) {
             // Yprev = the other half of the (Y, U) ping-pong; AX = rlx X + (1 - rlx) Yprev
             // (admm.py:877-885) with X rebuilt from that same previous iterate
             if (var == SPORCO_AMD_VAR_YPREV) {
                 SA_HIP(hipMemcpyAsync(rv(var), y_alt, sizeof(T) * E, hipMemcpyDeviceToDevice, st));
             } else {
-                const bool keep = prev_in_alt;
                 materialize_x();
-                prev_in_alt = keep;
                 ProfScope ps(prof, PS_OTHER);
                 launch_relax<T>(st, rv(SPORCO_AMD_VAR_X), y_alt, rv(SPORCO_AMD_VAR_AX),
                                 (T)last_p.rlx, E);
@@ -299,22 +297,10 @@
             }
             return false;
         }
-        FusedColsArgs<T> fa;
-        fa.t = cv(SPORCO_AMD_VAR_XF);
-        fa.dft = dft;
-        fa.sft = sft;
-        fa.gramt = gramt;
-        fa.twA = twA;
-        fa.twB = twB;
-        fa.rho = (T)p.rho;
-        fa.H = H;
-        fa.W = W;
-        fa.CN = CN;
-        fa.K = K;
-        fa.partials = part_f;
-        fa.Ks = Ks;
         const bool gradreg = p.flags & F_GRADREG;
-        const bool tail_ok = tail_mode;
+        // (striped: the single K <= 64 kernel without the gradient term only)
+        striped = striped && cols_striped() && !gradreg && !tail_mode && !fused_slabs;
+        auto fa = fused_cols_args(p.rho, striped);
         if (gradreg) {
             SA_REQUIRE(fused || fused_slabs, "no gradient-regularised column pass for this shape");
             const GradTerm<T> gt = grad_term(p.mu);
@@ -334,8 +320,7 @@
             fa.g1t = g1t;
         }
         int64_t ntiles;
-        bool did_stripe = false;
-        if (tail_ok) {
+        if (tail_mode) {
             // A handful of filters past 64 (the AddMaskSim impulse on a 64-filter dictionary):
             // they go through the generic column FFT, their inner products are folded into
             // Sf, and the register-resident kernel runs on the first 64 as if alone.
@@ -347,7 +332,6 @@
             const int64_t nt = (int64_t)Wf * CN, tstride = (int64_t)H * Ks;
             cx<T> *tail = fa.t + 64;
             fa.Kv = 64;
-            fa.Ks = Ks;
             fa.coef_out = coef_t;
             ProfScope ps(prof, PS_FUSED_COLS);
             fft_c2c<T>(st, planH, false, tail, tail, nt, Kt, tstride, Ks, tstride, Ks, T(1));
@@ -364,14 +348,8 @@
             ntiles = run_slab_cols(sa);
             if (gradreg) ntiles *= (K + 63) / 64;   // (one row of partials per tile and slab)
         } else {
-            striped = striped && cols_striped() && !gradreg;
-            if (striped) {
-                fa.out_even = cols_out[0];
-                fa.out_odd = cols_out[1];
-            }
             ProfScope ps(prof, PS_FUSED_COLS);
             ntiles = launch_fused_cols<T>(st, fa);
-            did_stripe = striped;
         }
         part_f_rows = (int)ntiles;
         xf_tiled = true;
@@ -381,32 +359,34 @@
             const int nv = gradreg ? 2 : 1;
             finalize(part_f, (int)ntiles, nv, nv, slots, scales, out_dev);
         }
-        return did_stripe;
+        return striped;
     }
 
     // One whole ADMM iteration in three launches (csc_rows.h): rows_fwd, fused_cols,
     // rows_inv_post.  X is written only on request (F_KEEP_X).
     void admm_iter_fused(const sporco_amd_admm_params &p, double *out_dev) {
         require_ready();
-        if (gv_live) ensure_yu();
         const bool keep_x = p.flags & F_KEEP_X;
+        const bool untouched = touch_epoch == fused_epoch;   // no host access since the last fused iteration
+        if (!keep_x && !y_alt) alloc_alt_pair();      // (may move Y, U and the spectrum buffer)
         // Single-array state (csc_rows.h): from the second fused iteration in a row with no host
         // access to the iterates in between, the epilogue stores V' = AX + U alone and the next
         // iteration derives (Y, U) from it -- seven passes instead of ten (six instead of eight
         // with an emitted spectrum).  Anything else that wants Y or U gets them through
         // ensure_yu() (var_ptr).
-        const bool nn = p.flags & F_NONNEG, jn = p.flags & F_JOINT;
-        if (v_live && (!vform_ok(p) || !vform_same_opts(p))) ensure_yu();
-        const bool vf = vform_ok(p) && (v_live || touch_epoch == fused_epoch);
-        T *vin = vf && v_live ? v_cur : nullptr;
-        if (!keep_x && !y_alt) alloc_alt_pair();      // (may move Y, U and the spectrum buffer)
+        const VRoute vr = enter_iteration(p, untouched);
+        T *const vin = vr.in.buf;
         T *Y = vin ? nullptr : rv(SPORCO_AMD_VAR_Y), *U = vin ? nullptr : rv(SPORCO_AMD_VAR_U);
         cx<T> *Xf = cv(SPORCO_AMD_VAR_XF);
-        T *vout = vf ? (vin == y_alt ? u_alt : y_alt) : nullptr;
         // rows_fwd, unless the previous iteration already left its result behind
         if (!(t_ready && p.u_scale == 1.0)) {
-            if (vin) launch_rows_fwd_on(nullptr, nullptr, (T)p.u_scale, vin, v_thr, p.flags, v_thr21, &p);
-            else launch_rows_fwd_on(Y, U, (T)p.u_scale);
+            if (vin) {
+                auto ra = rows_fwd_args(vr.in, p);
+                ra.s2 = (T)p.u_scale;
+                run_rows_fwd(ra);
+            } else {
+                launch_rows_fwd_on(Y, U, (T)p.u_scale);
+            }
         }
         t_ready = false;
         const bool striped = run_fused_cols(p, nullptr, !keep_x);
@@ -419,96 +399,36 @@
         // profiles/r02i_config3_*.json -- until the two elements of a pixel were serialised;
         // SPORCO_AMD_JOINT_EMIT=0 switches it off)
         const bool emit = stable_run >= 2 && !sw.no_speculation;
-        RowsPostArgs<T> pa;
-        pa.twA = twRows;
+        auto pa = rows_post_args(p, striped);
         pa.t_next = emit ? Xf : nullptr;
-        pa.t = Xf;
-        if (striped) {
-            pa.t = cols_out[0];
-            pa.t_odd = cols_out[1];
-        }
-        pa.twW = planW.tw<T>();
         pa.y = Y;
         pa.u = U;
         pa.y_out = keep_x ? Y : y_alt;
         pa.u_out = keep_x ? U : u_alt;
         pa.v_in = vin;
-        pa.v_out = vout;
-        pa.thr_prev = v_thr;
-        pa.thr21_prev = v_thr21;
+        pa.v_out = vr.out;
+        pa.thr_prev = vr.in.thr;
+        pa.thr21_prev = vr.in.thr21;
         pa.x = keep_x ? rv(SPORCO_AMD_VAR_X) : nullptr;
-        pa.scale = T(1.0 / ((double)H * (double)W));
-        pa.rlx = (T)p.rlx;
-        pa.thr = (T)(p.lmbda / p.rho);
+        pa.thr = (T)(p.lmbda / p.rho);    // (the host's scalars; under ctl the control block's)
         pa.thr21 = (T)(p.mu / p.rho);
         pa.u_scale = (T)p.u_scale;
-        pa.flags = p.flags;
-        pa.H = H;
-        pa.W = W;
-        pa.C = C;
-        pa.N = N;
-        pa.K = K;
-        pa.dH = p.dH;
-        pa.dW = p.dW;
-        pa.P = P;
-        pa.wl1 = wl1;
-        pa.Ks = Ks;
-        pa.ams_bits = ams_bits_of(p);
-        pa.ams_k = Ku - 1;
-        pa.partials = part_rows;
         int64_t nt;
         {
             ProfScope ps(prof, vin ? (emit ? PS_ROWS_INV_POST_V_EMIT : PS_ROWS_INV_POST_V)
                                    : (emit ? PS_ROWS_INV_POST_EMIT : PS_ROWS_INV_POST));
             nt = launch_rows_inv_post<T>(st, pa);
         }
-        if (p.flags & (F_RESID | F_OBJ)) {
-            // one launch sums both partial arrays: the six (joint: seven) epilogue sums and the
-            // data-fidelity term of the column kernel
-            const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                                  SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1,
-                                  SPORCO_AMD_OUT_L21};
-            const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
-            const int nrow = (p.flags & F_JOINT) ? 7 : 6;
-            const int fslots[2] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_RGR};
-            const double fscales[2] = {1.0 / ((double)H * W), 1.0 / ((double)H * W)};
-            const bool dfid = (p.flags & F_OBJ) && !(p.flags & F_FEVAL_Y);
-            const int fnv = (p.flags & F_GRADREG) ? 2 : 1;
-            ProfScope ps(prof, PS_FINALIZE);
-            launch_finalize2(st, part_rows, (int)nt, 8, nrow, slots, scales, part_f, part_f_rows, fnv,
-                             dfid ? fnv : 0, fslots, fscales, out_dev);
-        }
+        if (p.flags & (F_RESID | F_OBJ)) finalize_iter_sums(p, nt, out_dev);
         if (keep_x) {
             x_written();
-        } else if (vf) {
-            // the new iterate is the V in vout; the previous one is (Y, U) in vars (first V
-            // iteration) or the V this iteration read
-            v_prev_kind = vin ? 2 : 1;
-            v_prev_thr = v_thr;
-            v_prev_thr21 = v_thr21;
-            v_cur = vout;
-            v_thr = pa.thr;
-            v_thr21 = pa.thr21;
-            v_nonneg = nn;
-            v_joint = jn;
-            v_opts = p.flags & (F_NOBNDRY | F_AMS);
-            v_dH = p.dH;
-            v_dW = p.dW;
-            v_live = true;
-            vp_pending = false;
-            last_p = p;
-            x_stale = true;
-            x_invalid = p.flags & F_NO_X;
-            prev_in_alt = false;
+        } else if (vr.out) {
+            // the new iterate is the V in vr.out; the previous one is the V this iteration read, or
+            // (first V iteration) the (Y, U) in vars
+            const HeldV cur = held_v(p, vr.out, pa.thr, pa.thr21);
+            commit_v(p, cur, vin ? &vr.in : nullptr);
         } else {
-            // the new iterate lives in the alternate buffers: swap roles
-            std::swap(vars[SPORCO_AMD_VAR_Y], reinterpret_cast<void *&>(y_alt));
-            std::swap(vars[SPORCO_AMD_VAR_U], reinterpret_cast<void *&>(u_alt));
-            vp_pending = false;
-            last_p = p;
-            x_stale = true;
-            x_invalid = p.flags & F_NO_X;
-            prev_in_alt = true;
+            commit_yu(p);     // the new iterate lives in the alternate buffers
         }
         t_ready = emit;
         if ((p.flags & F_OBJ) && (p.flags & F_FEVAL_Y)) dfid_at(rv(SPORCO_AMD_VAR_Y), out_dev, &p);

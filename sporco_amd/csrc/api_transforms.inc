@@ -65,6 +65,142 @@
         launch_finalize(st, part, nblocks, stride, nvals, slots, scales, is_max, out_dev);
     }
 
+    // the sums of a three-launch iteration in one launch over both partial arrays: the six (joint:
+    // seven) of the `nt` row tiles of the epilogue, and the column kernel's data-fidelity (and
+    // gradient) term
+    void finalize_iter_sums(const sporco_amd_admm_params &p, int64_t nt, double *out_dev) {
+        const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
+                              SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1,
+                              SPORCO_AMD_OUT_L21};
+        const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
+        const int nrow = (p.flags & F_JOINT) ? 7 : 6;
+        const int fslots[2] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_RGR};
+        const double fscales[2] = {1.0 / ((double)H * W), 1.0 / ((double)H * W)};
+        const bool dfid = (p.flags & F_OBJ) && !(p.flags & F_FEVAL_Y);
+        const int fnv = (p.flags & F_GRADREG) ? 2 : 1;
+        ProfScope ps(prof, PS_FINALIZE);
+        launch_finalize2(st, part_rows, (int)nt, 8, nrow, slots, scales, part_f, part_f_rows, fnv,
+                         dfid ? fnv : 0, fslots, fscales, out_dev);
+    }
+
+    // ---- argument structs of the register-resident passes -------------------------------------
+    // Each builder sets every field that is the same wherever this handle launches the pass; a call
+    // site adds what is its own (the routing of the iterate, thresholds, ctl, tail / gradient extras).
+    // rows_fwd into the Xf buffer (rows Ks filters apart) or into `t` (rows of K filters)
+    RowsFwdArgs<T> rows_fwd_args(cx<T> *t = nullptr) {
+        RowsFwdArgs<T> ra;
+        ra.y = ra.u = nullptr;
+        ra.t = t ? t : cv(SPORCO_AMD_VAR_XF);
+        ra.Ks = t ? 0 : Ks;
+        ra.twA = twRows;
+        ra.H = H;
+        ra.W = W;
+        ra.C = C;
+        ra.N = N;
+        ra.CN = CN;
+        ra.K = K;
+        ra.P = P;
+        return ra;
+    }
+    // ... of an iterate held as V, with what the derivation of (Y, U) repeats: thresholds from the
+    // iterate, options from p -- the parameters of the iteration that reads it (the same options
+    // as the iterate's own: enter_iteration)
+    RowsFwdArgs<T> rows_fwd_args(const HeldV &v, const sporco_amd_admm_params &p, cx<T> *t = nullptr) {
+        RowsFwdArgs<T> ra = rows_fwd_args(t);
+        ra.v = v.buf;
+        ra.thr_prev = v.thr;
+        ra.thr21_prev = v.thr21;
+        ra.flags = p.flags;
+        ra.wl1 = wl1;
+        ra.dH = p.dH;
+        ra.dW = p.dW;
+        ra.ams_bits = ams_bits_of(p);
+        ra.ams_k = Ku - 1;
+        return ra;
+    }
+    void run_rows_fwd(const RowsFwdArgs<T> &ra) {
+        ProfScope ps(prof, ra.v ? PS_ROWS_FWD_V : PS_ROWS_FWD);
+        launch_rows_fwd<T>(st, ra);
+    }
+    void launch_rows_fwd_on(const T *Yin, const T *Uin, T s2) {
+        auto ra = rows_fwd_args();
+        ra.y = Yin;
+        ra.u = Uin;
+        ra.s2 = s2;
+        run_rows_fwd(ra);
+    }
+    // the column pass on the Xf buffer (or `t`) with the handle's dictionary and signal (striped: its
+    // output goes to cols_out[], csc_fused.h)
+    FusedColsArgs<T> fused_cols_args(double rho, bool striped = false, cx<T> *t = nullptr) {
+        FusedColsArgs<T> fa;
+        fa.t = t ? t : cv(SPORCO_AMD_VAR_XF);
+        fa.dft = dft;
+        fa.sft = sft;
+        fa.gramt = gramt;
+        fa.twA = twA;
+        fa.twB = twB;
+        fa.rho = (T)rho;
+        fa.H = H;
+        fa.W = W;
+        fa.CN = CN;
+        fa.K = K;
+        fa.partials = part_f;
+        fa.Ks = Ks;
+        if (striped) {
+            fa.out_even = cols_out[0];
+            fa.out_odd = cols_out[1];
+        }
+        return fa;
+    }
+    // the row epilogue reading the Xf buffer (striped: cols_out[]); no iterate routed, nothing
+    // emitted, no X: the call site sets those, thr / thr21 / u_scale and, where it has one, ctl
+    RowsPostArgs<T> rows_post_args(const sporco_amd_admm_params &p, bool striped = false) {
+        RowsPostArgs<T> pa;
+        pa.t = cv(SPORCO_AMD_VAR_XF);
+        if (striped) {
+            pa.t = cols_out[0];
+            pa.t_odd = cols_out[1];
+        }
+        pa.twW = planW.tw<T>();
+        pa.twA = twRows;
+        pa.t_next = nullptr;
+        pa.y = pa.u = nullptr;
+        pa.y_out = pa.u_out = nullptr;
+        pa.x = nullptr;
+        pa.scale = T(1.0 / ((double)H * (double)W));
+        pa.rlx = (T)p.rlx;
+        pa.flags = p.flags;
+        pa.H = H;
+        pa.W = W;
+        pa.C = C;
+        pa.N = N;
+        pa.K = K;
+        pa.dH = p.dH;
+        pa.dW = p.dW;
+        pa.P = P;
+        pa.wl1 = wl1;
+        pa.Ks = Ks;
+        pa.ams_bits = ams_bits_of(p);
+        pa.ams_k = Ku - 1;
+        pa.partials = part_rows;
+        return pa;
+    }
+    // the inverse row pass with a prox (FISTA; X on demand): transforms, dimensions, partials
+    RowsProxArgs<T> rows_prox_args() {
+        RowsProxArgs<T> ra;
+        ra.twA = twRows;
+        ra.twW = planW.tw<T>();
+        ra.scale = T(1.0 / ((double)H * (double)W));
+        ra.H = H;
+        ra.W = W;
+        ra.C = C;
+        ra.N = N;
+        ra.K = K;
+        ra.P = P;
+        ra.partials = part_rows;
+        return ra;
+    }
+
     // ---- tile-major operands of the fused X-step -----------------------------------
     void refresh_fused_dict() {
         if (fused_mc) {
@@ -95,24 +231,37 @@
                !(p.flags & (F_KEEP_X | F_FEVAL_Y | F_XRRS)) &&
                (!(p.flags & F_JOINT) || joint_rows_ok(p));
     }
-    // the live V was produced under the options of p (otherwise: back to (Y, U) first)
-    bool vform_same_opts(const sporco_amd_admm_params &p) const {
+    // the held V was produced under the options of p (otherwise: back to (Y, U) first)
+    static bool vform_same_opts(const HeldV &v, const sporco_amd_admm_params &p) {
         const uint32_t o = p.flags & (F_NOBNDRY | F_AMS);
-        return (bool)(p.flags & F_NONNEG) == v_nonneg && (bool)(p.flags & F_JOINT) == v_joint &&
-               o == v_opts && (!(o & F_NOBNDRY) || (p.dH == v_dH && p.dW == v_dW));
+        return (bool)(p.flags & F_NONNEG) == v.nonneg && (bool)(p.flags & F_JOINT) == v.joint &&
+               o == v.opts && (!(o & F_NOBNDRY) || (p.dH == v.dH && p.dW == v.dW));
     }
-    // Y (and / or U) of an iterate held as V: y or u may be null, u may alias v
-    void vform_split(const T *v, T *y, T *u, T thr, T thr21) {
-        if (v_joint)
-            launch_vform_split_joint<T>(st, v, y, u, thr, thr21, v_nonneg, C, (int64_t)N * K,
+    // an iterate that an iteration with the parameters p leaves (or left) as V in `buf`
+    static HeldV held_v(const sporco_amd_admm_params &p, T *buf, T thr, T thr21) {
+        HeldV v;
+        v.buf = buf;
+        v.thr = thr;
+        v.thr21 = thr21;
+        v.nonneg = p.flags & F_NONNEG;
+        v.joint = p.flags & F_JOINT;
+        v.opts = p.flags & (F_NOBNDRY | F_AMS);
+        v.dH = p.dH;
+        v.dW = p.dW;
+        return v;
+    }
+    // Y (and / or U) of an iterate held as V: y or u may be null, u may alias v.buf
+    void vform_split(const HeldV &v, T *y, T *u) {
+        if (v.joint)
+            launch_vform_split_joint<T>(st, v.buf, y, u, v.thr, v.thr21, v.nonneg, C, (int64_t)N * K,
                                         (int64_t)H * W);
-        else if (wl1.ptr || v_opts)
-            launch_vform_split_general<T>(st, v, y, u, thr,
-                                          (v_nonneg ? F_NONNEG : 0u) | (v_opts & F_NOBNDRY), d5(),
-                                          v_dH, v_dW, wl1, (v_opts & F_AMS) ? wams : Weight<T>(),
+        else if (wl1.ptr || v.opts)
+            launch_vform_split_general<T>(st, v.buf, y, u, v.thr,
+                                          (v.nonneg ? F_NONNEG : 0u) | (v.opts & F_NOBNDRY), d5(),
+                                          v.dH, v.dW, wl1, (v.opts & F_AMS) ? wams : Weight<T>(),
                                           Ku - 1);
         else
-            launch_vform_split<T>(st, v, y, u, thr, v_nonneg, E);
+            launch_vform_split<T>(st, v.buf, y, u, v.thr, v.nonneg, E);
     }
     // the generic chain keeps the single array too (admm_iter): plain l1 term, no option that
     // needs the 5-D index of an element or Y itself, and an X-step that reads (Y, U) through the
@@ -122,58 +271,90 @@
                !(p.flags & (F_JOINT | F_NOBNDRY | F_AMS | F_FEVAL_Y | F_XRRS)) &&
                !(rows_ok && (fused || fused_slabs || fused_mc));
     }
+    T *other_alt(const T *b) const { return b == y_alt ? u_alt : y_alt; }
+    void swap_alt_pair() {
+        std::swap(vars[SPORCO_AMD_VAR_Y], reinterpret_cast<void *&>(y_alt));
+        std::swap(vars[SPORCO_AMD_VAR_U], reinterpret_cast<void *&>(u_alt));
+    }
+    // ---- transitions of the iterate record (csc_api.hip `it`) ---------------------------------
+    // Entry of a fused iteration or run with the parameters p.  A held V that p cannot continue goes
+    // back to (Y, U); `in` is the V the first iteration reads (buf null: it reads (Y, U) from vars),
+    // `out` the buffer its V' goes to (null: the (Y, U) form).  A live V is always continued; want_v
+    // says whether the caller enters the V form from (Y, U).  The alt pair must exist by now.
+    struct VRoute {
+        HeldV in;
+        T *out = nullptr;
+    };
+    VRoute enter_iteration(const sporco_amd_admm_params &p, bool want_v) {
+        if (it.form == IterForm::GenericV) ensure_yu();
+        if (it.form == IterForm::FusedV && !(vform_ok(p) && vform_same_opts(it.cur, p))) ensure_yu();
+        VRoute r;
+        const bool live = it.form == IterForm::FusedV;
+        if (!live && !(want_v && vform_ok(p))) return r;
+        if (live) r.in = it.cur;
+        r.out = other_alt(r.in.buf);
+        return r;
+    }
+    // what both forms of a fused iteration leave behind: X exists on demand (materialize_x, from the
+    // previous iterate and last_p)
+    void commit_common(const sporco_amd_admm_params &p) {
+        last_p = p;
+        x_stale = true;
+        x_invalid = p.flags & F_NO_X;
+    }
+    // ... in the V form: `cur` is the new iterate, `prev` the V before it (in the other alt buffer),
+    // or null when the previous iterate is the (Y, U) in vars that the only iteration read
+    void commit_v(const sporco_amd_admm_params &p, const HeldV &cur, const HeldV *prev) {
+        if (prev) it.prev = *prev;
+        it.prev_at = prev ? PrevAt::AltV : PrevAt::VarsYU;
+        it.cur = cur;
+        it.form = IterForm::FusedV;
+        commit_common(p);
+    }
+    // ... in the (Y, U) form: the new iterate went to (y_alt, u_alt) and the pairs swap roles
+    void commit_yu(const sporco_amd_admm_params &p) {
+        swap_alt_pair();
+        it.prev_at = PrevAt::AltYU;
+        commit_common(p);
+    }
     void ensure_yu() {
-        if (gv_live) {
-            gv_live = false;
-            ProfScope ps(prof, PS_OTHER);
-            T *ub = static_cast<T *>(vars[SPORCO_AMD_VAR_U]);
-            launch_vform_split<T>(st, ub, static_cast<T *>(vars[SPORCO_AMD_VAR_Y]), ub, gv_thr,
-                                  gv_nonneg, E);
+        if (it.form == IterForm::YU) return;
+        const bool generic = it.form == IterForm::GenericV;
+        it.form = IterForm::YU;
+        ProfScope ps(prof, PS_OTHER);
+        T *const Yv = static_cast<T *>(vars[SPORCO_AMD_VAR_Y]), *const Uv = static_cast<T *>(vars[SPORCO_AMD_VAR_U]);
+        HeldV cur = it.cur;
+        if (generic) {     // in place: V lives in the buffer of U
+            cur.buf = Uv;
+            vform_split(cur, Yv, Uv);
             return;
         }
-        if (!v_live) return;
-        v_live = false;
-        T *other = v_cur == y_alt ? u_alt : y_alt;
-        ProfScope ps(prof, PS_OTHER);
-        if (v_prev_kind == 1) {
+        T *other = other_alt(cur.buf);
+        if (it.prev_at == PrevAt::VarsYU) {
             // vars hold the previous iterate as (Y, U) and the other alt buffer is free: the
-            // new pair goes to (other, v_cur) and the buffers trade places -- exactly the state
+            // new pair goes to (other, cur.buf) and the buffers trade places -- exactly the state
             // an iteration of the (Y, U) form leaves behind
-            vform_split(v_cur, other, v_cur, v_thr, v_thr21);
-            T *oldY = static_cast<T *>(vars[SPORCO_AMD_VAR_Y]), *oldU = static_cast<T *>(vars[SPORCO_AMD_VAR_U]);
+            vform_split(cur, other, cur.buf);
             vars[SPORCO_AMD_VAR_Y] = other;
-            vars[SPORCO_AMD_VAR_U] = v_cur;
-            y_alt = oldY;
-            u_alt = oldU;
-            prev_in_alt = true;
+            vars[SPORCO_AMD_VAR_U] = cur.buf;
+            y_alt = Yv;
+            u_alt = Uv;
+            it.prev_at = PrevAt::AltYU;
         } else {
-            vform_split(v_cur, static_cast<T *>(vars[SPORCO_AMD_VAR_Y]),
-                        static_cast<T *>(vars[SPORCO_AMD_VAR_U]), v_thr, v_thr21);
-            // the previous iterate stays in V form until somebody asks for it
-            vp_pending = v_prev_kind == 2;
-            vp_buf = other;
-            vp_free = v_cur;
-            vp_thr = v_prev_thr;
-            vp_thr21 = v_prev_thr21;
-            vp_nonneg = v_nonneg;
-            prev_in_alt = false;
+            vform_split(cur, Yv, Uv);
+            // the previous iterate (it.prev, in `other`) stays in V form until somebody asks for it
+            it.prev_at = it.prev_at == PrevAt::AltV ? PrevAt::PendingV : PrevAt::None;
+            it.prev_free = cur.buf;
         }
-        v_cur = nullptr;
     }
     void ensure_prev_yu() {
         ensure_yu();
-        if (!vp_pending) return;
-        vp_pending = false;
+        if (it.prev_at != PrevAt::PendingV) return;
         ProfScope ps(prof, PS_OTHER);
-        {
-            const bool nn = v_nonneg;
-            v_nonneg = vp_nonneg;
-            vform_split(vp_buf, vp_free, vp_buf, vp_thr, vp_thr21);
-            v_nonneg = nn;
-        }
-        y_alt = vp_free;
-        u_alt = vp_buf;
-        prev_in_alt = true;
+        vform_split(it.prev, it.prev_free, it.prev.buf);
+        y_alt = it.prev_free;
+        u_alt = it.prev.buf;
+        it.prev_at = PrevAt::AltYU;
     }
 
     // X of the last three-launch iteration, rebuilt from the previous iterate.
@@ -221,9 +402,8 @@
         pgm_rx_count = 0;
         if ((x_stale && !x_invalid) || pgm_x_stale || md_x_pending) materialize_x();
         ensure_yu();
-        vp_pending = false;
+        it.prev_at = PrevAt::None;
         t_ready = false;
-        prev_in_alt = false;
     }
     // The dictionary changes: a pending X depends on the old one, but the speculatively emitted
     // row spectra of Y - U (t_ready) and the ping-pong parity do not -- a dictionary-learning

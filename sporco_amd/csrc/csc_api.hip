@@ -171,7 +171,8 @@ template <typename T> struct Csc : CscBase {
     // L1Weight, NonNegCoef, NoBndryCross), ConvBPDNJoint, ConvBPDNGradReg, AddMaskSim and mask
     // decoupling with K <= 256; FISTA and the tile-major dictionary update with K <= 64
     // (csc_rows_body.inc, csc_pgm_body.inc, csc_fused.h); LinSolveCheck, multi-channel dictionaries
-    // and consensus stay on the generic chain for such a handle (include/sporco_amd.h).
+    // and consensus (cns_fused()) stay on the generic chain for such a handle, and so does an
+    // iteration with an L21Weight array (mr_ok()); the support matrix is in include/sporco_amd.h.
     bool mr = false;
     bool mr_ok(const sporco_amd_admm_params &p) const {
         return !mr || (Cd == 1 && !wl21.ptr && !(p.flags & F_XRRS));
@@ -192,34 +193,44 @@ template <typename T> struct Csc : CscBase {
     T *y_alt = nullptr, *u_alt = nullptr;
     bool x_stale = false, x_invalid = false;
     bool md_x_pending = false;   // X of a fused mask-decoupled iteration: rows_inverse of the Xf buffer
-    // after a three-launch iteration the previous iterate sits in y_alt and AX was never
-    // formed: a host read of VAR_YPREV / VAR_AX derives them (download)
-    bool prev_in_alt = false;
-    // Single-array state of the fused iteration (csc_rows.h, "V form").  While v_live, the
-    // current iterate is V = AX + U of the iteration that produced it, in v_cur (one of y_alt /
-    // u_alt, which ping-pong as V buffers); vars[Y] / vars[U] then hold the iterate the run
-    // started from (v_prev_kind 1: it is the previous iterate) or stale data (v_prev_kind 2:
-    // the previous iterate is the V in the other alt buffer, produced with v_prev_thr).
-    // ensure_yu() returns the handle to the (Y, U) form every other code path expects;
-    // ensure_prev_yu() also brings the previous iterate back into (y_alt, u_alt).
-    bool v_live = false;
-    T *v_cur = nullptr;
-    T v_thr = T(0), v_prev_thr = T(0);
-    T v_thr21 = T(0), v_prev_thr21 = T(0), vp_thr21 = T(0);   // ConvBPDNJoint: the l2,1 thresholds
-    bool v_nonneg = false, v_joint = false;
-    uint32_t v_opts = 0;     // F_NOBNDRY | F_AMS of the iterations that produced the V's
-    int v_dH = 1, v_dW = 1;  // ... and their filter support (NoBndryCross)
-    int v_prev_kind = 0;
-    bool vp_pending = false;       // the previous iterate still waits, in V form, in vp_buf
-    T *vp_buf = nullptr, *vp_free = nullptr;
-    T vp_thr = T(0);
-    bool vp_nonneg = false;
+    // ---- where the ADMM iterate is (`it`) ---------------------------------------------------
+    // An iterate held as the single array V = AX + U of the iteration that produced it (csc_rows.h,
+    // "V form"), with that iteration's thresholds and options: what the derivation Y = prox(V),
+    // U = V - Y repeats.  The options travel with every held iterate (held_v fills them from the
+    // iteration's parameters).
+    struct HeldV {
+        T *buf = nullptr;
+        T thr = T(0), thr21 = T(0);   // lambda / rho; ConvBPDNJoint: mu / rho, the l2,1 threshold
+        bool nonneg = false, joint = false;
+        uint32_t opts = 0;            // F_NOBNDRY | F_AMS
+        int dH = 1, dW = 1;           // filter support (NoBndryCross)
+        uint32_t flags() const { return (nonneg ? F_NONNEG : 0u) | (joint ? F_JOINT : 0u) | opts; }
+    };
+    enum class IterForm {
+        YU,        // (Y, U) in vars: the form every code path but the two below expects
+        FusedV,    // it.cur, in one of y_alt / u_alt (which ping-pong as V buffers); vars[Y] / vars[U]
+                   // hold the iterate the run started from (PrevAt::VarsYU) or stale data
+        GenericV   // the generic chain (api_admm.inc admm_iter): V in the buffer of vars[U], updated in
+                   // place (vars[Y] is stale); it.cur carries thr and nonneg, no buffer, no previous V
+    };
+    enum class PrevAt {
+        None,       // unknown, or gone
+        VarsYU,     // FusedV: (Y, U) in vars -- the first iteration of the run read them
+        AltV,       // FusedV: it.prev, the V in the other alt buffer
+        PendingV,   // YU: still it.prev, in V form, until somebody asks (ensure_prev_yu); it.prev_free is
+                    // the alt buffer beside it
+        AltYU       // YU: (Y, U) in (y_alt, u_alt), the other half of the ping-pong; AX was never
+                    // formed: a host read of VAR_YPREV / VAR_AX derives them (download)
+    };
+    // Transitions: enter_iteration / commit_v / commit_yu (the two fused drivers, api_transforms.inc),
+    // commit_generic_v (api_admm.inc), ensure_yu / ensure_prev_yu / before_state_change.
+    struct IterState {
+        IterForm form = IterForm::YU;
+        PrevAt prev_at = PrevAt::None;
+        HeldV cur, prev;
+        T *prev_free = nullptr;
+    } it;
     uint64_t touch_epoch = 0, fused_epoch = ~(uint64_t)0;   // host accesses between fused iterations
-    // The generic chain's single-array state (api_admm.inc admm_iter): while gv_live the iterate
-    // is V = AX + U in the buffer of vars[U] (updated in place; vars[Y] is stale), produced with
-    // the threshold gv_thr.  Never live together with v_live; ensure_yu() resolves either.
-    bool gv_live = false, gv_nonneg = false;
-    T gv_thr = T(0);
     uint64_t gen_epoch = ~(uint64_t)0;
     // t_ready: the Xf buffer already holds rows_fwd(Y, U, s = 1) of the current
     // iterate, emitted by the previous rows_inv_post on the bet that rho stays put
@@ -349,7 +360,10 @@ template <typename T> struct Csc : CscBase {
             if (fused_mr_height(H)) fused = fused_slabs = false;
             mr = false;
         }
-        if (mr) cols256 = false;      // (consensus, mask decoupling, the K > 64 families: generic)
+        // (what asks for cols256 alone -- the consensus update, cns_fused() -- takes the generic chain;
+        // FISTA and the tile-major dictionary update ask `cols256 || mr`, and the ADMM iterations, mask
+        // decoupling and the slab column pass for 64 < K <= 256 do not ask at all: mr_ok())
+        if (mr) cols256 = false;
         // (a mixed-radix height has no tail form: 64 < K <= 72 runs two slabs there)
         tail_mode = fused_slabs && K - 64 <= kTailMax && !fused_mr_height(H);
         Ks = (rows_ok && tail_mode) ? 80 : K;
@@ -478,7 +492,7 @@ template <typename T> struct Csc : CscBase {
         SA_REQUIRE(var_is_valid(var), "unknown state variable id");
         if (var == SPORCO_AMD_VAR_Y || var == SPORCO_AMD_VAR_U) {
             ++touch_epoch;
-            if (v_live || gv_live) ensure_yu();
+            ensure_yu();
         }
         if (!vars[var]) {
             const size_t nb = var_alloc_bytes(var);
@@ -587,7 +601,7 @@ template <typename T> struct Csc : CscBase {
         if (what == SPORCO_AMD_QUERY_FUSED_ROWS) return rows_ok ? 1 : 0;
         if (what == SPORCO_AMD_QUERY_FUSED_PGM) return pgm_fused_ok() ? 1 : 0;
         if (what == SPORCO_AMD_QUERY_DEVICE_FILTERS) return K;
-        if (what == SPORCO_AMD_QUERY_VFORM_LIVE) return (v_live || gv_live) ? 1 : 0;
+        if (what == SPORCO_AMD_QUERY_VFORM_LIVE) return it.form != IterForm::YU ? 1 : 0;
         if (what == SPORCO_AMD_QUERY_PERSIST_RUNS) return pst_runs;
         if (what == SPORCO_AMD_QUERY_CCMOD_GROUPS) return ccmod_group_count();
         throw Error(SPORCO_AMD_EINVAL, "unknown query");

@@ -21,7 +21,9 @@ from test_fused_xstep import problem
 FIELDS = ('ObjFun', 'DFid', 'RegL1', 'PrimalRsdl', 'DualRsdl', 'EpsPrimal', 'EpsDual', 'Rho')
 
 
-def run(D, S, optd, vform, host=False, lmbda=0.05, calls=1, joint_mu=None):
+def run(D, S, optd, vform, host=False, lmbda=0.05, calls=1, joint_mu=None, reverse=False):
+    """reverse: read the iterates in the order AX, Yprev, X, U, Y instead of Y, U, X, Yprev, AX, so
+    that the previous iterate is asked for while the handle still holds the current one as V."""
     from sporco_amd import _lib
     from sporco_amd.admm import cbpdn
     env = {}
@@ -40,8 +42,11 @@ def run(D, S, optd, vform, host=False, lmbda=0.05, calls=1, joint_mu=None):
             b._return_min = False         # (solve() without fetching Y: the state stays put)
             b.solve()
             live.append(b._dev.query(_lib.QUERY_VFORM_LIVE))
-        out = dict(Y=b.Y.copy(), U=b.U.copy(), X=b.X.copy(), Yprev=b._fetch(_lib.VAR_YPREV).copy(),
-                   AX=b._fetch(_lib.VAR_AX).copy(), k=b.k, live=live,
+        reads = {'Y': lambda: b.Y, 'U': lambda: b.U, 'X': lambda: b.X,
+                 'Yprev': lambda: b._fetch(_lib.VAR_YPREV), 'AX': lambda: b._fetch(_lib.VAR_AX)}
+        order = ('Y', 'U', 'X', 'Yprev', 'AX')
+        out = {f: reads[f]().copy() for f in (order[::-1] if reverse else order)}
+        out.update(k=b.k, live=live,
                    stats={f: np.asarray(getattr(b.getitstat(), f), float) for f in FIELDS}
                    if b.itstat else {})
     finally:
@@ -87,6 +92,50 @@ def test_v_form_is_bit_identical_to_the_yu_form(backend, case, host):
     # from its second iteration on
     if o1['k'] >= 2 or not host:
         assert o1['live'] == [1], (case, host, o1['k'])
+    same(o0, o1)
+
+
+@pytest.mark.parametrize('case', ['default', 'nonneg_period3', 'stops_at_once'])
+@pytest.mark.parametrize('host', [False, True])
+def test_v_form_read_back_previous_iterate_first(backend, case, host):
+    """AX and Yprev are read BEFORE Y and U: the previous iterate is brought back to (Y, U) while
+    the current one is still held as V (the other tests read Y first, which converts the current
+    iterate before the previous one is asked for).  Same contract: the (Y, U) form, bit for bit."""
+    H = 256 if backend == 'gpu' else 128
+    K, N = (16, 3) if backend == 'gpu' else (4, 2)
+    D, S = problem(H, H, K, N, seed=11)
+    optd = CASES[case]
+    b0, o0 = run(D, S, optd, vform=False, host=host, reverse=True)
+    b1, o1 = run(D, S, optd, vform=True, host=host, reverse=True)
+    assert b1._dev.uses_fused_rows()
+    assert o0['live'] == [0]
+    if o1['k'] >= 2 or not host:
+        assert o1['live'] == [1], (case, host, o1['k'])
+    same(o0, o1)
+
+
+@pytest.mark.parametrize('variant', ['joint', 'nobndry_nonneg_weight'])
+def test_v_form_read_back_previous_iterate_first_under_options(backend, variant):
+    """The same read order where the split of a held V repeats options: ConvBPDNJoint (the joint
+    split kernel) and NoBndryCross + NonNegCoef + an L1Weight array (the general one)."""
+    H = 256 if backend == 'gpu' else 128
+    if variant == 'joint':
+        C, N, K = 3, (2 if backend == 'gpu' else 1), 32
+        D, S = problem(H, H, K, N, seed=21, C=C)
+        # (kept short on the CPU simulator)
+        optd = {'MaxMainIter': 6 if backend == 'gpu' else 4, 'RelStopTol': 0.0}
+        kw = dict(lmbda=0.1, joint_mu=0.02)
+    else:
+        K, N = (16, 3) if backend == 'gpu' else (4, 2)
+        D, S = problem(H, H, K, N, seed=15)
+        w = (0.5 + np.abs(np.random.RandomState(3).randn(H, H, 1, 1, K))).astype(np.float32)
+        optd = {'MaxMainIter': 7, 'RelStopTol': 0.0, 'NoBndryCross': True, 'NonNegCoef': True,
+                'L1Weight': w}
+        kw = {}
+    b0, o0 = run(D, S, optd, vform=False, reverse=True, **kw)
+    b1, o1 = run(D, S, optd, vform=True, reverse=True, **kw)
+    assert b1._dev.uses_fused_rows() and b1._fused_ok()
+    assert o0['live'] == [0] and o1['live'] == [1]
     same(o0, o1)
 
 
