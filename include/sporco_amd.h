@@ -119,6 +119,8 @@ typedef struct {
 #define SPORCO_AMD_VAR_WMS 24  /* real  (H,W,C,N,K) ConvBPDNInhib: self inhibition weights                  */
 #define SPORCO_AMD_VAR_TVY 25  /* real  (3,H,W,C,N,K) ConvBPDNScalarTV / VectorTV: the blocks (y_0, y_1, y_L) of Y */
 #define SPORCO_AMD_VAR_TVU 26  /* real  (3,H,W,C,N,K) ... and of U                                              */
+#define SPORCO_AMD_VAR_RTVY1 27 /* real (H,W,C,N,2) ConvBPDNRecTV: the gradient block of Y (its coefficient block is VAR_Y) */
+#define SPORCO_AMD_VAR_RTVU1 28 /* real (H,W,C,N,2) ... and of U (coefficient block: VAR_U)                               */
 /* Dictionary-sized state of the D-step (pgm.ccmod.ConvCnstrMOD, admm.ccmod consensus Y =
  * DX): real (H,W,K) / complex (H,Wf,K).  Ids 19..31 are reserved. */
 #define SPORCO_AMD_VAR_DX 32      /* real  dictionary iterate X (zero-padded filters)    */
@@ -736,6 +738,36 @@ int sporco_amd_csc_tv_ystep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
  * VAR_U <- q = u_scale (the same of U); out[S2] = sum (p - previous VAR_Y)^2 -- the dual residual
  * ||A^T (Y - Yprev)||^2 of admm.py:745-752 without its rho --, out[U2] = sum q^2 (:765-775). */
 int sporco_amd_csc_tv_adjoint(sporco_amd_csc_t h, double u_scale, double out[SPORCO_AMD_OUT_COUNT]);
+
+/* ---- ConvBPDNRecTV (sporco/admm/cbpdntv.py:733-1356): total variation of the reconstruction ----
+ * The constraint is (I; Gamma_0; Gamma_1) x = (y0; y1), Gamma_i x = G_i sum_m w_m d_m * x_m.  The
+ * coefficient blocks of Y and U are the handle's VAR_Y / VAR_U, the gradient blocks VAR_RTVY1 /
+ * VAR_RTVU1, (H, W, C, N, 2) with the gradient component fastest.  The reference's rank-3 iterated
+ * Sherman-Morrison has two collinear rows per frequency: the system is ConvBPDN's rank-one system
+ * with the scale 1 + rho w^2 GHGf for equal TVWeights and a rank-two (2 x 2 Woodbury) system for
+ * different ones; G_i and G_i^T are stencils on signal-shaped maps (csrc/csc_rtv.h).
+ * An iteration is rtv_xstep, rtv_ystep, rtv_dual, driven from the host.  Single-channel real
+ * dictionaries, H, W >= 2, no volume handles; every K-map transform is the generic chain's.
+ * tvw: n = 1 (scalar) or n = K weights.  rtv_setup also computes the spectra of the blocks the
+ * handle holds; after uploading a Y0 / U0 into the four block variables call rtv_dual once. */
+int sporco_amd_csc_rtv_setup(sporco_amd_csc_t h, const double *tvw, int32_t n);
+/* Profile slot "rtv_solve": Xf from rfftn(y0), rfftn(u0) and the adjoint-map spectra that the last
+ * rtv_dual left (params.u_scale applied to the U side), X = irfftn(Xf), and the weighted
+ * reconstruction irfftn(sum_m w_m Df_m Xf_m) for the y step.  out[DFID] with FLAG_OBJ (unless
+ * FLAG_FEVAL_Y), out[XRRS_*] with FLAG_XRRS (the residual of the system actually solved). */
+int sporco_amd_csc_rtv_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]);
+/* Profile slot "rtv_ystep" (two launches: coefficient block, gradient block): relax_AX (:1319-1339),
+ * y0 = prox_l1(. , (lmbda / rho) L1Weight), y1 = prox_l2 over (channel, component) per pixel with
+ * mu / rho (:1098-1106), U += AX - Y.  out[R2], out[AX2], out[Y2] over both blocks, out[L1] =
+ * sum |L1Weight g0|, out[L21] = sum sqrt(sum_{c,i} g1^2), g at Y with FLAG_GEVAL_Y, else at AXnr. */
+int sporco_amd_csc_rtv_ystep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]);
+/* Profile slot "rtv_dual" (+ the transform slots): the spectra of the blocks as they stand, out[S2] =
+ * ||A^T (Y - Yprev)||^2 (Yprev: the blocks at the previous call), out[U2] = ||A^T U||^2 (admm.py:722-775
+ * without rho), and with FLAG_OBJ | FLAG_FEVAL_Y out[DFID] at rfftn(y0).  Uses params.flags only. */
+int sporco_amd_csc_rtv_dual(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]);
 
 /* ---- online dictionary learning (sporco.dictlrn.onlinecdl.OnlineConvBPDNDictLearn.dstep,
  * onlinecdl.py:310-333) -------------------------------------------------------------------

@@ -20,6 +20,7 @@ VAR_MY0, VAR_MU0 = 19, 20
 VAR_DMY0, VAR_DMU0 = 21, 22
 VAR_WML, VAR_WMS = 23, 24
 VAR_TVY, VAR_TVU = 25, 26
+VAR_RTVY1, VAR_RTVU1 = 27, 28
 VAR_DX, VAR_DXF, VAR_DYF, VAR_DXFPRV, VAR_DYFPRV = 32, 33, 34, 35, 36
 VAR_DVF, VAR_DGF, VAR_DT0, VAR_DT1, VAR_DT2 = 37, 38, 39, 40, 41
 VAR_DSX, VAR_DSU = 42, 43
@@ -83,6 +84,7 @@ EXPORTS = (
     'sporco_amd_csc_set_data_mask', 'sporco_amd_csc_masked_grad',
     'sporco_amd_csc_inhib_setup', 'sporco_amd_csc_inhib_update',
     'sporco_amd_csc_tv_setup', 'sporco_amd_csc_tv_xstep', 'sporco_amd_csc_tv_ystep', 'sporco_amd_csc_tv_adjoint',
+    'sporco_amd_csc_rtv_setup', 'sporco_amd_csc_rtv_xstep', 'sporco_amd_csc_rtv_ystep', 'sporco_amd_csc_rtv_dual',
     'sporco_amd_csc_profile', 'sporco_amd_csc_profile_read', 'sporco_amd_profile_slots',
     'sporco_amd_dev_malloc', 'sporco_amd_dev_free', 'sporco_amd_dev_upload',
     'sporco_amd_dev_download', 'sporco_amd_dev_axpby', 'sporco_amd_tikhonov_filter_dev',
@@ -301,6 +303,10 @@ def load(path=None):
         'sporco_amd_csc_tv_xstep': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_tv_ystep': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_tv_adjoint': [vp, dbl, dptr],
+        'sporco_amd_csc_rtv_setup': [vp, dptr, i32],
+        'sporco_amd_csc_rtv_xstep': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_rtv_ystep': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_rtv_dual': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_mdcpl_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_dstep_init': [vp, vp],
         'sporco_amd_csc_dstep_md_init': [vp, vp, vp],
@@ -480,6 +486,8 @@ class Solver(object):
             return (H, W, N, self.Cd, K), self.dtype
         if var in (VAR_TVY, VAR_TVU):
             return (3, H, W, C, N, K), self.dtype
+        if var in (VAR_RTVY1, VAR_RTVU1):
+            return (H, W, C, N, 2), self.dtype
         return (H, W, C, N, K), self.dtype
 
     # -- set-up -----------------------------------------------------------
@@ -732,6 +740,33 @@ class Solver(object):
         sums."""
         out = self._out()
         check(self._lib.sporco_amd_csc_tv_adjoint(self._h, float(u_scale), out))
+        return list(out)
+
+    def rtv_setup(self, tvw):
+        """ConvBPDNRecTV state (sporco_amd_csc_rtv_setup): ``tvw`` a scalar or one weight per filter."""
+        w = np.ascontiguousarray(tvw, dtype=np.float64).ravel()
+        if w.size not in (1, self.dims[4]):
+            raise ValueError("TVWeight must be a scalar or hold one value per filter")
+        check(self._lib.sporco_amd_csc_rtv_setup(
+            self._h, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), w.size))
+
+    def rtv_xstep(self, params):
+        """The x step of ConvBPDNRecTV (sporco_amd_csc_rtv_xstep); returns the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_rtv_xstep(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def rtv_ystep(self, params):
+        """relax + y step + u step of ConvBPDNRecTV (sporco_amd_csc_rtv_ystep); returns the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_rtv_ystep(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def rtv_dual(self, params):
+        """The spectra of the blocks and the dual residual norms (sporco_amd_csc_rtv_dual); returns
+        the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_rtv_dual(self._h, ctypes.byref(params), out))
         return list(out)
 
     def admm_iter_dev(self, params, out_dev_ptr):

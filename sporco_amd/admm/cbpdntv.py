@@ -1,9 +1,12 @@
 """ADMM convolutional sparse coding with total-variation terms on the GPU.
 
-Drop-in for the first two classes of the reference's ``sporco.admm.cbpdntv`` (ConvBPDNScalarTV
-sporco/admm/cbpdntv.py:31-571, ConvBPDNVectorTV :577-727): same constructor signature, Options
-tree, IterationStats fields, attributes (``X, Y, U, D, S, rho, lmbda, mu, Wl1, Wtv, cri, itstat``)
-and the ``var_y0 / var_y1 / var_yx``, ``cnst_*``, ``obfn_*`` methods.
+Drop-in for the classes of the reference's ``sporco.admm.cbpdntv`` (ConvBPDNScalarTV
+sporco/admm/cbpdntv.py:31-571, ConvBPDNVectorTV :577-727, ConvBPDNRecTV :733-1356): same
+constructor signature, Options tree, IterationStats fields, attributes (``X, Y, U, D, S, rho, lmbda,
+mu, Wl1, Wtv, cri, itstat``) and the ``var_y0 / var_y1 / var_yx``, ``cnst_*``, ``obfn_*`` methods.
+:class:`ConvBPDNRecTV`, the total variation of the reconstruction, is described at the class.
+
+The first two classes:
 
 The constraint is ``(Gamma_0; Gamma_1; I) x = (y_0; y_1; y_L)``: ``Y`` and ``U`` have three blocks
 (``cri.shpX + (3,)``).  The x step is the system of :class:`sporco_amd.admm.cbpdn.ConvBPDNGradReg`
@@ -26,7 +29,7 @@ from .. import _lib
 from .. import cnvrep as cr
 from ..fft import real_dtype
 
-__all__ = ['ConvBPDNScalarTV', 'ConvBPDNVectorTV']
+__all__ = ['ConvBPDNScalarTV', 'ConvBPDNVectorTV', 'ConvBPDNRecTV']
 
 
 class ConvBPDNScalarTV(admm.ADMM):
@@ -108,7 +111,7 @@ class ConvBPDNScalarTV(admm.ADMM):
         self.xrrs = None
 
         Nx = int(np.prod(np.array(self.cri.shpX)))
-        yshape = self.cri.shpX + (len(self.cri.axisN) + 1,)
+        yshape = self._yshape()
         super(ConvBPDNScalarTV, self).__init__(Nx, yshape, yshape, S.dtype, opt)
 
         rdt = real_dtype(self.dtype).type
@@ -141,6 +144,9 @@ class ConvBPDNScalarTV(admm.ADMM):
             self.Y = np.asarray(opt['Y0']).astype(self.dtype, copy=True)
         if opt['U0'] is not None:
             self.U = np.asarray(opt['U0']).astype(self.dtype, copy=True)
+
+    def _yshape(self):
+        return self.cri.shpX + (len(self.cri.axisN) + 1,)
 
     # -- device state -------------------------------------------------------------------------
     def init_state(self, yshape, ushape):
@@ -431,3 +437,193 @@ class ConvBPDNVectorTV(ConvBPDNScalarTV):
     axis (per pixel, channel and signal); everything else is :class:`ConvBPDNScalarTV`."""
 
     _vector_tv = True
+
+
+class ConvBPDNRecTV(ConvBPDNScalarTV):
+    r"""Convolutional BPDN with a total-variation term on the reconstruction: minimise
+    (1/2)||sum_m d_m * x_m - s||_2^2 + lambda sum_m ||x_m||_1 +
+    mu || sqrt(sum_i (G_i sum_m w_m d_m * x_m)^2) ||_1 (reference class:
+    sporco/admm/cbpdntv.py:733-1356); for multi-channel signals the l2 norm also runs over the
+    channels.
+
+    The constraint is ``(I; Gamma_0; Gamma_1) x = (y_0; y_1)``: ``Y`` and ``U`` have the shape of
+    ``X`` with ``M + 2`` entries on the filter axis, the coefficient block first
+    (``block_sep0 / block_sep1 / block_cat``).  The reference solves the x step as a rank-3 iterated
+    Sherman-Morrison; its two gradient rows are collinear per frequency, so the device solves a
+    rank-one system (scalar or equal ``TVWeight``) or a rank-two one (different weights per filter)
+    in closed form, and applies the gradient operators as stencils on signal-shaped maps
+    (csrc/csc_rtv.h).  Per iteration: ``rtv_xstep``, ``rtv_ystep``, ``rtv_dual``, driven from the host.
+
+    In scope and refused: as :class:`ConvBPDNScalarTV`.  ``LinSolveCheck`` reports the residual of
+    the system the device solves, which is the reference's system.
+
+    IterationStats fields: ``Iter, ObjFun, DFid, RegL1, RegTV, PrimalRsdl, DualRsdl, EpsPrimal,
+    EpsDual, Rho, XSlvRelRes, Time``.
+    """
+
+    class Options(ConvBPDNScalarTV.Options):
+        """ConvBPDN's options plus ``TVWeight`` (cbpdntv.py:823-846): a scalar, or one weight per
+        filter."""
+
+    def _yshape(self):
+        yshape = list(self.cri.shpX)
+        yshape[self.cri.axisM] += len(self.cri.axisN) * self.cri.Cd
+        return tuple(yshape)
+
+    def _upload_weights(self):
+        if self.Wl1.size == 1:
+            self._wl1_scalar = float(self.Wl1.ravel()[0])
+            self._dev.set_l1_weight(None)
+        else:
+            self._wl1_scalar = 1.0
+            self._dev.set_l1_weight(cbpdn._broadcastable(self.Wl1, self.cri.shpX))
+        self._dev.rtv_setup(np.asarray(self.Wtv, dtype=np.float64).ravel())
+        self._tv_ready = True
+
+    # -- the blocks on the device: (VAR_Y, VAR_RTVY1) and (VAR_U, VAR_RTVU1) ------------------------
+    _block_vars = {'Y': (_lib.VAR_Y, _lib.VAR_RTVY1), 'U': (_lib.VAR_U, _lib.VAR_RTVU1)}
+
+    def _fetch_blocks(self, which):
+        if which not in self._cache:
+            v0, v1 = self._block_vars[which]
+            a = np.concatenate((self._dev.download(v0), self._dev.download(v1)), axis=self.cri.axisM)
+            if which == 'U' and self._u_scale != 1.0:
+                a *= a.dtype.type(self._u_scale)
+            self._cache[which] = a
+        return self._cache[which]
+
+    def _store_blocks(self, which, value):
+        value = np.asarray(value, dtype=self.dtype)
+        shp = self._yshape()
+        if value.size != int(np.prod(shp)):
+            raise ValueError("array of shape %s is not a two-block array of shape %s" % (value.shape, shp))
+        value = value.reshape(shp)
+        v0, v1 = self._block_vars[which]
+        self._dev.upload(v0, np.ascontiguousarray(value[..., :self.cri.M]))
+        self._dev.upload(v1, np.ascontiguousarray(value[..., self.cri.M:]))
+        if which == 'U':
+            self._u_scale = 1.0
+        self._touch(which)
+        if self._tv_ready:
+            self._dev.rtv_dual(self._params())      # the spectra the x step reads
+
+    @property
+    def Y(self):
+        """The coefficient block and the gradient block on the filter axis, ``M + 2`` entries, as
+        the reference keeps them."""
+        return self._fetch_blocks('Y')
+
+    @Y.setter
+    def Y(self, value):
+        if value is not None:
+            self._store_blocks('Y', value)
+
+    @property
+    def U(self):
+        return self._fetch_blocks('U')
+
+    @U.setter
+    def U(self, value):
+        if value is not None:
+            self._store_blocks('U', value)
+
+    def block_sep0(self, Y):
+        """The coefficient block of Y (cbpdntv.py:972-975)."""
+        return Y[..., 0:self.cri.M]
+
+    def block_sep1(self, Y):
+        """The gradient block of Y, the gradient index on a new last axis (cbpdntv.py:979-995)."""
+        return np.swapaxes(Y[..., self.cri.M:, np.newaxis], self.cri.axisM, -1)
+
+    def block_cat(self, Y0, Y1):
+        """(cbpdntv.py:999-1022)"""
+        return np.concatenate((Y0, np.swapaxes(Y1, self.cri.axisM, -1)[..., 0]), axis=self.cri.axisM)
+
+    def var_y0(self):
+        return self.block_sep0(self.Y)
+
+    def var_y1(self):
+        return self.block_sep1(self.Y)
+
+    def var_yx(self):
+        return self.var_y0()
+
+    def var_yx_idx(self):
+        return np.s_[..., 0:self.cri.M]
+
+    def getmin(self):
+        return self.X if self.opt['ReturnX'] else self.var_y0()
+
+    # -- the constraint on host arrays (cbpdntv.py:1237-1315) ---------------------------------------
+    def _host_wdf(self):
+        return self.Wtv * np.fft.rfftn(np.asarray(self.D, dtype=np.float64), self.cri.Nv, self.cri.axisN)
+
+    def cnst_A0(self, X):
+        return X
+
+    def cnst_A0T(self, Y0):
+        return Y0
+
+    def cnst_A1(self, X, Xf=None):
+        """G_i (sum_m w_m d_m * x_m), the gradient index last: (H, W, C, N, 1, 2)."""
+        if Xf is None:
+            Xf = np.fft.rfftn(np.asarray(X), axes=self.cri.axisN)
+        R = np.fft.irfftn(np.sum(self._host_wdf() * Xf, axis=self.cri.axisM, keepdims=True), self.cri.Nv,
+                          self.cri.axisN)
+        return np.stack([R - np.roll(R, 1, axis=i) for i in self.cri.axisN], axis=-1)
+
+    def cnst_A1T(self, Y1):
+        """Gamma_i^T y_1i per gradient index (last axis): (H, W, C, N, M, 2)."""
+        Y1 = np.asarray(Y1)
+        Z = np.stack([Y1[..., i] - np.roll(Y1[..., i], -1, axis=ax) for i, ax in enumerate(self.cri.axisN)],
+                     axis=-1)
+        Zf = np.fft.rfftn(Z, axes=self.cri.axisN)
+        return np.fft.irfftn(np.conj(self._host_wdf())[..., np.newaxis] * Zf, self.cri.Nv, self.cri.axisN)
+
+    def cnst_A(self, X, Xf=None):
+        return self.block_cat(self.cnst_A0(X), self.cnst_A1(X, Xf))
+
+    def cnst_AT(self, Y):
+        return self.cnst_A0T(self.block_sep0(Y)) + np.sum(self.cnst_A1T(self.block_sep1(Y)), axis=-1)
+
+    # -- iteration ----------------------------------------------------------------------------
+    def xstep(self):
+        """The rank-one / rank-two closed form of the reference's rank-3 system
+        (cbpdntv.py:1026-1094; csrc/csc_rtv.h)."""
+        out = self._dev.rtv_xstep(self._params())
+        for slot in (_lib.OUT_DFID, _lib.OUT_XRRS_D2, _lib.OUT_XRRS_AX2, _lib.OUT_XRRS_B2):
+            self._sums[slot] = out[slot]
+        self._touch(_lib.VAR_X, _lib.VAR_XF)
+        if self.opt['LinSolveCheck']:
+            s = self._sums
+            nrm = max(np.sqrt(s[_lib.OUT_XRRS_AX2]), np.sqrt(s[_lib.OUT_XRRS_B2]))
+            self.xrrs = 0.0 if nrm == 0.0 else np.sqrt(s[_lib.OUT_XRRS_D2]) / nrm
+        else:
+            self.xrrs = None
+
+    def _yu_steps(self):
+        """relax_AX, ystep and ustep (``rtv_ystep``), then the spectra of the new blocks and the
+        dual residual norms (``rtv_dual``)."""
+        p = self._params()
+        out = self._dev.rtv_ystep(p)
+        for slot in (_lib.OUT_R2, _lib.OUT_AX2, _lib.OUT_Y2, _lib.OUT_L1, _lib.OUT_L21):
+            self._sums[slot] = out[slot]
+        self._u_scale = 1.0
+        out = self._dev.rtv_dual(p)
+        for slot in (_lib.OUT_S2, _lib.OUT_U2):
+            self._sums[slot] = out[slot]
+        if not self.opt['fEvalX']:
+            self._sums[_lib.OUT_DFID] = out[_lib.OUT_DFID]
+        self._touch('Y', 'U')
+
+    def relax_AX(self):
+        """Part of ``rtv_ystep`` (cbpdntv.py:1319-1339)."""
+
+    def ystep(self):
+        """Part of ``rtv_ystep`` (cbpdntv.py:1098-1106)."""
+
+    def rescale_u(self, rsf):
+        """Defer ``U /= rsf`` (admm.py:573): the factor rides along as ``u_scale``; the x step applies
+        it to the spectra of U and ``rtv_ystep`` to its blocks."""
+        self._u_scale = self._u_scale / float(rsf)
+        self._touch('U')

@@ -175,7 +175,7 @@
     void host_copy(int var, void *host, bool to_device) {
         void *dev = var_ptr(var);
         const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-        if (K == Ku || var == SPORCO_AMD_VAR_SF || var_is_signal_real(var)) {
+        if (K == Ku || var == SPORCO_AMD_VAR_SF || var_is_signal_real(var) || var_is_rtv_grad(var)) {
             if (to_device) SA_HIP(hipMemcpyAsync(dev, host, var_bytes(var), kind, st));
             else SA_HIP(hipMemcpyAsync(host, dev, var_bytes(var), kind, st));
             return;

@@ -629,6 +629,47 @@ int sporco_amd_csc_tv_adjoint(sporco_amd_csc_t h, double u_scale, double out[SPO
     SA_API_END
 }
 
+int sporco_amd_csc_rtv_setup(sporco_amd_csc_t h, const double *tvw, int32_t n) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(tvw != nullptr, "null TVWeight");
+    h->impl->rtv_setup(tvw, n);
+    SA_API_END
+}
+
+int sporco_amd_csc_rtv_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->rtv_xstep(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
+int sporco_amd_csc_rtv_ystep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->rtv_ystep(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
+int sporco_amd_csc_rtv_dual(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->rtv_dual(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
 int sporco_amd_csc_dstep_init(sporco_amd_csc_t h, const void *Y0) {
     SA_API_BEGIN
     SA_HANDLE(h);

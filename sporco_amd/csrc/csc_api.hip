@@ -26,7 +26,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                            "admm_persist_run",
                                     "setcoef_rows",     "setcoef_cols",     "ccmod_grad_tiled",
                                     "fft_c2r_vpost",    "fft_c2r_vpost_emit",
-                                    "inhib_update",     "tv_ystep",         "tv_adjoint"};
+                                    "inhib_update",     "tv_ystep",         "tv_adjoint",
+                                    "rtv_solve",        "rtv_ystep",        "rtv_dual"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -431,6 +432,7 @@ template <typename T> struct Csc : CscBase {
         place_release_spares();
         inhib_release();
         tv_release();
+        rtv_release();
         big_free(gemit);
         if (part_vpost) (void)hipFree(part_vpost);
         big_free(cols_out[0]);
@@ -471,6 +473,7 @@ template <typename T> struct Csc : CscBase {
     static bool var_is_signal_real(int var) {
         return var >= SPORCO_AMD_VAR_MY0 && var <= SPORCO_AMD_VAR_DMU0;
     }
+    static bool var_is_rtv_grad(int var) { return var == SPORCO_AMD_VAR_RTVY1 || var == SPORCO_AMD_VAR_RTVU1; }
     size_t var_bytes(int var) const {
         if (var == SPORCO_AMD_VAR_SF) return sizeof(cx<T>) * npix * CNs;
         if (var_is_signal_real(var)) return sizeof(T) * (int64_t)H * W * CNs;
@@ -481,6 +484,8 @@ template <typename T> struct Csc : CscBase {
         if (var == SPORCO_AMD_VAR_CX || var == SPORCO_AMD_VAR_CU) return sizeof(T) * E * Cd;
         // (the three blocks of the TV classes' Y and U, one after the other)
         if (var == SPORCO_AMD_VAR_TVY || var == SPORCO_AMD_VAR_TVU) return sizeof(T) * E * 3;
+        // (the gradient blocks of ConvBPDNRecTV: two maps per image, no filter axis)
+        if (var_is_rtv_grad(var)) return sizeof(T) * (int64_t)H * W * CN * 2;
         return var_is_complex(var) ? sizeof(cx<T>) * EF : sizeof(T) * E;
     }
 
@@ -619,6 +624,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_dstep.inc"
 #include "api_inhib.inc"
 #include "api_tv.inc"
+#include "api_rtv.inc"
 };
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

@@ -19,6 +19,7 @@
 #include "csc_kernels.h"
 #include "csc_pgm.h"
 #include "csc_rows.h"
+#include "csc_rtv.h"
 #include "csc_tv.h"
 #include "fft.h"
 
@@ -89,6 +90,9 @@ enum ProfSlot {
     PS_INHIB,                   // ConvBPDNInhib: the inhibition-weight update (csc_inhib.h)
     PS_TV_YSTEP,                // ConvBPDNScalarTV / VectorTV: relax + y step + u step + sums (csc_tv.h)
     PS_TV_ADJOINT,              // ... and P = A^T Y, Q = A^T U with the dual-residual sums
+    PS_RTV_SOLVE,               // ConvBPDNRecTV: the rank-one / rank-two x step solve (csc_rtv.h)
+    PS_RTV_YSTEP,               // ... relax + y step + u step + sums, coefficient and gradient block
+    PS_RTV_DUAL,                // ... the adjoint maps and the frequency-domain residual norms
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -224,6 +228,10 @@ struct CscBase {
     virtual void tv_xstep(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void tv_ystep(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void tv_adjoint(double u_scale, double *out_dev) = 0;
+    virtual void rtv_setup(const double *tvw, int n) = 0;
+    virtual void rtv_xstep(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void rtv_ystep(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void rtv_dual(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void read_out(const double *out_dev, double *out_host) = 0;
     double *out_dev_default = nullptr;
     Profiler prof;
@@ -266,7 +274,7 @@ static bool var_is_dict_sized(int var) {
 }
 
 static bool var_is_valid(int var) {
-    return (var >= 0 && var <= SPORCO_AMD_VAR_TVU) ||
+    return (var >= 0 && var <= SPORCO_AMD_VAR_RTVU1) ||
            (var >= SPORCO_AMD_VAR_DX && var < SPORCO_AMD_VAR_COUNT);
 }
 
