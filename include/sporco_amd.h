@@ -122,7 +122,7 @@ typedef struct {
 #define SPORCO_AMD_VAR_RTVY1 27 /* real (H,W,C,N,2) ConvBPDNRecTV: the gradient block of Y (its coefficient block is VAR_Y) */
 #define SPORCO_AMD_VAR_RTVU1 28 /* real (H,W,C,N,2) ... and of U (coefficient block: VAR_U)                               */
 /* Dictionary-sized state of the D-step (pgm.ccmod.ConvCnstrMOD, admm.ccmod consensus Y =
- * DX): real (H,W,K) / complex (H,Wf,K).  Ids 19..31 are reserved. */
+ * DX): real (H,W,K) / complex (H,Wf,K).  Ids 29..31 are reserved. */
 #define SPORCO_AMD_VAR_DX 32      /* real  dictionary iterate X (zero-padded filters)    */
 #define SPORCO_AMD_VAR_DXF 33     /* cplx  rfftn(DX)                                     */
 #define SPORCO_AMD_VAR_DYF 34     /* cplx  auxiliary (momentum) state                    */
@@ -198,6 +198,10 @@ int sporco_amd_csc_stream(sporco_amd_csc_t h, void **stream);
 #define SPORCO_AMD_QUERY_CCMOD_GROUPS 6  /* image groups per row frequency of the tile-major
                                           * dictionary-update gradient (their partial gradients
                                           * are written and summed: bench.py's byte model) */
+#define SPORCO_AMD_QUERY_PD_WAVE_LAUNCHES 7     /* how many pd_xstep calls of this handle ran the wave
+                                                * form of pd_solve (the system in registers) ...        */
+#define SPORCO_AMD_QUERY_PD_GENERIC_LAUNCHES 8  /* ... and how many the one-thread-per-system form --
+                                                * diagnostics, so that a test can tell the two apart */
 int sporco_amd_csc_query(sporco_amd_csc_t h, int what, int *out);
 /* Diagnostics, no reference counterpart: where the handle put the X-sized arrays that one kernel
  * writes at the same time (the spectrum buffer T and the iterate buffers of the fused ADMM
@@ -768,6 +772,32 @@ int sporco_amd_csc_rtv_ystep(sporco_amd_csc_t h, const sporco_amd_admm_params *p
  * without rho), and with FLAG_OBJ | FLAG_FEVAL_Y out[DFID] at rfftn(y0).  Uses params.flags only. */
 int sporco_amd_csc_rtv_dual(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
                             double out[SPORCO_AMD_OUT_COUNT]);
+
+/* ---- ConvProdDictBPDN / ConvProdDictBPDNJoint (sporco/admm/pdcsc.py:28-287): product dictionary ----
+ * minimise (1/2) || D X B^T - S ||^2 + lambda ||X||_1 (+ mu ||X||_2,1 over the channel axis), D a
+ * single-channel convolutional dictionary, B (Cs x Cb) a standard dictionary over the channel axis.
+ * The handle is created with C = Cb channels (those of the coefficient maps) and its signal slot is
+ * given the mixed signal S (B Q), (H, W, Cb, N), through sporco_amd_csc_set_signal, B^T B = Q Gamma Q^T.
+ * Y, U, X, the weights, admm_relax / admm_ystep (FLAG_JOINT for the joint class) / admm_ustep /
+ * admm_stats are the handle's own; the x step, the data fidelity at Y and the reconstruction are the
+ * calls below (csrc/csc_pd.h).  Single-channel real dictionaries, Cb <= 16, no volume handles; every
+ * K-map transform is the generic chain's; the iteration is driven from the host.
+ * pd_setup: B (cs x Cb) and Q (Cb x Cb) row-major, gamma (Cb) >= 0, S the cs-channel signal
+ * (H, W, cs, N) in the handle's dtype.  A second call replaces the state of the first. */
+int sporco_amd_csc_pd_setup(sporco_amd_csc_t h, const double *B, const double *Q, const double *gamma,
+                            const void *S, int32_t cs);
+/* Profile slot "pd_solve" (+ the transform slots): zf = rfftn(Y - u_scale U); per frequency and image
+ * zh = Q^T z, xh_c' = (b - conj(d) gamma_c' (d.b) / (rho + gamma_c' |d|^2)) / rho with b = conj(d) sh_c' +
+ * rho zh_c', x = Q xh; X = irfftn(Xf).  K even with K / 2 a power of two <= 64 and Cb <= 8: the system
+ * in registers, sums by wave shuffles; otherwise one thread per system.  out[DFID] = ||B Df.Xf - Sf||^2
+ * with FLAG_OBJ (unless FLAG_FEVAL_Y), out[XRRS_*] with FLAG_XRRS (in eigen-coordinates). */
+int sporco_amd_csc_pd_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]);
+/* Profile slot "pd_recon": out[DFID] = ||B sum_m Df_m rfftn(var)_m - Sf||^2 (half-spectrum Parseval) of
+ * a real K-map variable -- the data fidelity at Y when fEvalX is off. */
+int sporco_amd_csc_pd_dfid(sporco_amd_csc_t h, int var, double out[SPORCO_AMD_OUT_COUNT]);
+/* out (H, W, cs, N) = irfftn(B sum_m Df_m rfftn(var)_m), host memory. */
+int sporco_amd_csc_pd_reconstruct(sporco_amd_csc_t h, int var, void *out);
 
 /* ---- online dictionary learning (sporco.dictlrn.onlinecdl.OnlineConvBPDNDictLearn.dstep,
  * onlinecdl.py:310-333) -------------------------------------------------------------------

@@ -42,6 +42,7 @@ FLAG_DMASK = 1 << 12
 QUERY_FUSED_COLS, QUERY_FUSED_ROWS, QUERY_FUSED_PGM, QUERY_DEVICE_FILTERS, QUERY_VFORM_LIVE = 0, 1, 2, 3, 4
 QUERY_PERSIST_RUNS = 5
 QUERY_CCMOD_GROUPS = 6
+QUERY_PD_WAVE_LAUNCHES, QUERY_PD_GENERIC_LAUNCHES = 7, 8
 HINT_KEEP_VFORM = 0
 HINT_ONE_LAUNCH = 1
 MODE_COMPLEX_PAIR = 2
@@ -85,6 +86,7 @@ EXPORTS = (
     'sporco_amd_csc_inhib_setup', 'sporco_amd_csc_inhib_update',
     'sporco_amd_csc_tv_setup', 'sporco_amd_csc_tv_xstep', 'sporco_amd_csc_tv_ystep', 'sporco_amd_csc_tv_adjoint',
     'sporco_amd_csc_rtv_setup', 'sporco_amd_csc_rtv_xstep', 'sporco_amd_csc_rtv_ystep', 'sporco_amd_csc_rtv_dual',
+    'sporco_amd_csc_pd_setup', 'sporco_amd_csc_pd_xstep', 'sporco_amd_csc_pd_dfid', 'sporco_amd_csc_pd_reconstruct',
     'sporco_amd_csc_profile', 'sporco_amd_csc_profile_read', 'sporco_amd_profile_slots',
     'sporco_amd_dev_malloc', 'sporco_amd_dev_free', 'sporco_amd_dev_upload',
     'sporco_amd_dev_download', 'sporco_amd_dev_axpby', 'sporco_amd_tikhonov_filter_dev',
@@ -307,6 +309,10 @@ def load(path=None):
         'sporco_amd_csc_rtv_xstep': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_rtv_ystep': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_rtv_dual': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_pd_setup': [vp, dptr, dptr, dptr, vp, i32],
+        'sporco_amd_csc_pd_xstep': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_pd_dfid': [vp, i32, dptr],
+        'sporco_amd_csc_pd_reconstruct': [vp, i32, vp],
         'sporco_amd_csc_mdcpl_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_dstep_init': [vp, vp],
         'sporco_amd_csc_dstep_md_init': [vp, vp, vp],
@@ -768,6 +774,40 @@ class Solver(object):
         out = self._out()
         check(self._lib.sporco_amd_csc_rtv_dual(self._h, ctypes.byref(params), out))
         return list(out)
+
+    def pd_setup(self, B, Q, gamma, S):
+        """Product-dictionary state (sporco_amd_csc_pd_setup): ``B`` (Cs, Cb), ``Q`` (Cb, Cb), ``gamma``
+        (Cb) and the Cs-channel signal ``S`` (H, W, Cs, N).  The handle's own signal is S (B Q)."""
+        H, W, Cb, N, K = self.dims
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64).ravel()
+        if B.ndim != 2 or B.shape[1] != Cb or Q.shape != (Cb, Cb) or gamma.size != Cb:
+            raise ValueError("B must be (Cs, %d), Q (%d, %d) and gamma hold %d values" % (Cb, Cb, Cb, Cb))
+        self.pd_Cs = int(B.shape[0])
+        S = _carr(S, self.dtype).reshape(H, W, self.pd_Cs, N)
+        dp = ctypes.POINTER(ctypes.c_double)
+        check(self._lib.sporco_amd_csc_pd_setup(self._h, B.ctypes.data_as(dp), Q.ctypes.data_as(dp),
+                                                gamma.ctypes.data_as(dp), _ptr(S), self.pd_Cs))
+
+    def pd_xstep(self, params):
+        """The x step of ConvProdDictBPDN (sporco_amd_csc_pd_xstep); returns the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_pd_xstep(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def pd_dfid(self, var):
+        """||B sum_m Df_m rfftn(var)_m - Sf||^2 (sporco_amd_csc_pd_dfid)."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_pd_dfid(self._h, int(var), out))
+        return out[OUT_DFID]
+
+    def pd_reconstruct(self, var):
+        """irfftn(B sum_m Df_m rfftn(var)_m), (H, W, Cs, N) (sporco_amd_csc_pd_reconstruct)."""
+        H, W, Cb, N, K = self.dims
+        out = np.empty((H, W, self.pd_Cs, N), dtype=self.dtype)
+        check(self._lib.sporco_amd_csc_pd_reconstruct(self._h, int(var), _ptr(out)))
+        return out
 
     def admm_iter_dev(self, params, out_dev_ptr):
         check(self._lib.sporco_amd_csc_admm_iter_dev(self._h, ctypes.byref(params),

@@ -196,8 +196,13 @@ class GenericConvBPDN(admm.ADMMEqual):
             self._dev.set_signal_dev(self._S_dev.ptr)
         else:
             self.S = np.asarray(S.reshape(self.cri.shpS), dtype=self.dtype)
-            self._dev.set_signal(self.S)
+            self._upload_signal()
         self.setdict()
+
+    def _upload_signal(self):
+        """The host signal into the handle (a class whose handle holds another array in its
+        signal slot overrides this)."""
+        self._dev.set_signal(self.S)
 
     def _fold(self, a):
         """(depth, height, ...) -> (depth * height, ...) of a dimN = 3 array; arrays that broadcast
@@ -1155,6 +1160,8 @@ class AddMaskSim(object):
         self.cri = cr.CSC_ConvRepIndexing(D, S, dimK=dimK, dimN=dimN)
         if not hasattr(cbpdnclass, '_set_ams'):
             raise TypeError("AddMaskSim wraps the solver classes of sporco_amd.admm.cbpdn")
+        if getattr(cbpdnclass, '_ams_refusal', None):      # (a class with another constructor signature)
+            raise NotImplementedError(cbpdnclass._ams_refusal)
         # impulse filter -- one per channel of a multi-channel dictionary -- appended to the
         # dictionary (cbpdn.py:2337-2346)
         if self.cri.Cd == 1:

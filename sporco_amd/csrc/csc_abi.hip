@@ -670,6 +670,44 @@ int sporco_amd_csc_rtv_dual(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
     SA_API_END
 }
 
+int sporco_amd_csc_pd_setup(sporco_amd_csc_t h, const double *B, const double *Q, const double *gamma,
+                            const void *S, int32_t cs) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(B && Q && gamma && S, "null argument");
+    h->impl->pd_setup(B, Q, gamma, S, cs);
+    SA_API_END
+}
+
+int sporco_amd_csc_pd_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                            double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->pd_xstep(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
+int sporco_amd_csc_pd_dfid(sporco_amd_csc_t h, int var, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->pd_dfid(var, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
+int sporco_amd_csc_pd_reconstruct(sporco_amd_csc_t h, int var, void *out) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    h->impl->pd_reconstruct(var, out);
+    SA_API_END
+}
+
 int sporco_amd_csc_dstep_init(sporco_amd_csc_t h, const void *Y0) {
     SA_API_BEGIN
     SA_HANDLE(h);

@@ -27,7 +27,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "setcoef_rows",     "setcoef_cols",     "ccmod_grad_tiled",
                                     "fft_c2r_vpost",    "fft_c2r_vpost_emit",
                                     "inhib_update",     "tv_ystep",         "tv_adjoint",
-                                    "rtv_solve",        "rtv_ystep",        "rtv_dual"};
+                                    "rtv_solve",        "rtv_ystep",        "rtv_dual",
+                                    "pd_solve",         "pd_recon"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -433,6 +434,7 @@ template <typename T> struct Csc : CscBase {
         inhib_release();
         tv_release();
         rtv_release();
+        pd_release();
         big_free(gemit);
         if (part_vpost) (void)hipFree(part_vpost);
         big_free(cols_out[0]);
@@ -609,6 +611,8 @@ template <typename T> struct Csc : CscBase {
         if (what == SPORCO_AMD_QUERY_VFORM_LIVE) return it.form != IterForm::YU ? 1 : 0;
         if (what == SPORCO_AMD_QUERY_PERSIST_RUNS) return pst_runs;
         if (what == SPORCO_AMD_QUERY_CCMOD_GROUPS) return ccmod_group_count();
+        if (what == SPORCO_AMD_QUERY_PD_WAVE_LAUNCHES) return pd_wave_launches;
+        if (what == SPORCO_AMD_QUERY_PD_GENERIC_LAUNCHES) return pd_generic_launches;
         throw Error(SPORCO_AMD_EINVAL, "unknown query");
     }
 
@@ -625,6 +629,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_inhib.inc"
 #include "api_tv.inc"
 #include "api_rtv.inc"
+#include "api_pd.inc"
 };
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

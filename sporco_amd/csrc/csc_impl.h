@@ -17,6 +17,7 @@
 #include "csc_fused.h"
 #include "csc_inhib.h"
 #include "csc_kernels.h"
+#include "csc_pd.h"
 #include "csc_pgm.h"
 #include "csc_rows.h"
 #include "csc_rtv.h"
@@ -93,6 +94,8 @@ enum ProfSlot {
     PS_RTV_SOLVE,               // ConvBPDNRecTV: the rank-one / rank-two x step solve (csc_rtv.h)
     PS_RTV_YSTEP,               // ... relax + y step + u step + sums, coefficient and gradient block
     PS_RTV_DUAL,                // ... the adjoint maps and the frequency-domain residual norms
+    PS_PD_SOLVE,                // ConvProdDictBPDN: the eigen-channel rank-one x step solve (csc_pd.h)
+    PS_PD_RECON,                // ... the reconstruction spectrum through B (reconstruct, fidelity at Y)
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -232,6 +235,10 @@ struct CscBase {
     virtual void rtv_xstep(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void rtv_ystep(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void rtv_dual(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void pd_setup(const double *B, const double *Q, const double *gamma, const void *S, int cs) = 0;
+    virtual void pd_xstep(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void pd_dfid(int var, double *out_dev) = 0;
+    virtual void pd_reconstruct(int var, void *dst) = 0;
     virtual void read_out(const double *out_dev, double *out_host) = 0;
     double *out_dev_default = nullptr;
     Profiler prof;
