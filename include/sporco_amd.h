@@ -202,6 +202,18 @@ int sporco_amd_csc_stream(sporco_amd_csc_t h, void **stream);
                                                 * form of pd_solve (the system in registers) ...        */
 #define SPORCO_AMD_QUERY_PD_GENERIC_LAUNCHES 8  /* ... and how many the one-thread-per-system form --
                                                 * diagnostics, so that a test can tell the two apart */
+#define SPORCO_AMD_QUERY_COLS_SM_FORM 9  /* which form of the one-kernel column pass of the generic
+                                          * X-step (forward transform along H, Sherman-Morrison solve,
+                                          * inverse transform of a tile held in LDS) the handle's last
+                                          * such launch took, or -1 when it has made none (the height
+                                          * has a factor the pass does not serve, SPORCO_AMD_NO_COLS_SM,
+                                          * a fused path).  Bits 0-11: threads per workgroup (256 or
+                                          * 1024); bits 12-15: rows of solve operands a thread requests
+                                          * together (float32 4, 8 or 12; float64 2, 4 or 6; 4 in the
+                                          * slab form); bit 16: 1 for the instantiation that carries the
+                                          * 6-, 10- and 12-point butterflies; bits 17 and up: filters
+                                          * per slab, 0 when the whole tile fits LDS -- diagnostics, so
+                                          * that a test can tell which instantiation it exercised */
 int sporco_amd_csc_query(sporco_amd_csc_t h, int what, int *out);
 /* Diagnostics, no reference counterpart: where the handle put the X-sized arrays that one kernel
  * writes at the same time (the spectrum buffer T and the iterate buffers of the fused ADMM

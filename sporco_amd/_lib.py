@@ -43,6 +43,7 @@ QUERY_FUSED_COLS, QUERY_FUSED_ROWS, QUERY_FUSED_PGM, QUERY_DEVICE_FILTERS, QUERY
 QUERY_PERSIST_RUNS = 5
 QUERY_CCMOD_GROUPS = 6
 QUERY_PD_WAVE_LAUNCHES, QUERY_PD_GENERIC_LAUNCHES = 7, 8
+QUERY_COLS_SM_FORM = 9
 HINT_KEEP_VFORM = 0
 HINT_ONE_LAUNCH = 1
 MODE_COMPLEX_PAIR = 2

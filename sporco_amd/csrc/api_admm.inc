@@ -119,7 +119,7 @@
             {
                 ProfScope ps(prof, PS_SM_SOLVE);
                 nt = fft_cols_sm<T>(st, planH, Xf, cv(SPORCO_AMD_VAR_DF), cv(SPORCO_AMD_VAR_SF), gram,
-                                    (T)p.rho, Wf, CN, K, W, obj, part_cs, sw.cols_sm_force_slab);
+                                    (T)p.rho, Wf, CN, K, W, obj, part_cs, sw.cols_sm_force_slab, &cols_sm_form);
             }
             if (obj) {
                 const int slots[1] = {SPORCO_AMD_OUT_DFID};
@@ -158,6 +158,7 @@
     // channel dictionary, plain system (no gradient term, no LinSolveCheck residual), the
     // epilogue not deferred into the row pass
     double *part_cs = nullptr;
+    ColsSmForm cols_sm_form;      // what the last fft_cols_sm call launched (threads 0: none yet)
     bool cols_sm_ok(const sporco_amd_admm_params &p) const {
         return Cd == 1 && depth == 1 && !(p.flags & (F_GRADREG | F_XRRS)) && !sw.no_cols_sm &&
                fft_cols_sm_supported<T>(planH, K, sw.cols_sm_force_slab);
@@ -348,7 +349,7 @@
         {
             ProfScope ps(prof, PS_SM_SOLVE);
             nt = fft_cols_sm<T>(st, planH, Xf, cv(SPORCO_AMD_VAR_DF), cv(SPORCO_AMD_VAR_SF), gram, (T)p.rho, Wf, CN,
-                                K, W, obj, part_cs, sw.cols_sm_force_slab);
+                                K, W, obj, part_cs, sw.cols_sm_force_slab, &cols_sm_form);
         }
         if (obj) {
             const int slots[1] = {SPORCO_AMD_OUT_DFID};

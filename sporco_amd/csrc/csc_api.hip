@@ -613,6 +613,7 @@ template <typename T> struct Csc : CscBase {
         if (what == SPORCO_AMD_QUERY_CCMOD_GROUPS) return ccmod_group_count();
         if (what == SPORCO_AMD_QUERY_PD_WAVE_LAUNCHES) return pd_wave_launches;
         if (what == SPORCO_AMD_QUERY_PD_GENERIC_LAUNCHES) return pd_generic_launches;
+        if (what == SPORCO_AMD_QUERY_COLS_SM_FORM) return cols_sm_form.threads ? cols_sm_form.packed() : -1;
         throw Error(SPORCO_AMD_EINVAL, "unknown query");
     }
 

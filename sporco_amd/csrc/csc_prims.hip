@@ -19,6 +19,21 @@ struct DevBuf {
     template <typename U> U *as() { return static_cast<U *>(p); }
 };
 
+// the two plans of a 2-D transform, released on every way out (a refused length throws)
+struct Plans {
+    FftPlan w, h;
+    Plans(int W, int H) {
+        w.init(W);
+        h.init(H);
+    }
+    ~Plans() {
+        w.destroy();
+        h.destroy();
+    }
+    Plans(const Plans &) = delete;
+    Plans &operator=(const Plans &) = delete;
+};
+
 void require_gpu() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
@@ -28,29 +43,23 @@ void require_gpu() {
 template <typename T> void prim_rfftn2(int H, int W, int64_t P, const void *in, void *out) {
     const int64_t Wf = W / 2 + 1;
     DevBuf din(sizeof(T) * H * W * P), dout(sizeof(cx<T>) * H * Wf * P);
-    FftPlan pw, ph;
-    pw.init(W);
-    ph.init(H);
+    Plans pl(W, H);
+    const FftPlan &pw = pl.w, &ph = pl.h;
     SA_HIP(hipMemcpy(din.p, in, sizeof(T) * H * W * P, hipMemcpyHostToDevice));
     rfft2<T>(nullptr, pw, ph, din.as<T>(), nullptr, T(0), dout.as<cx<T>>(), H, W, P);
     SA_HIP(hipDeviceSynchronize());
     SA_HIP(hipMemcpy(out, dout.p, sizeof(cx<T>) * H * Wf * P, hipMemcpyDeviceToHost));
-    pw.destroy();
-    ph.destroy();
 }
 
 template <typename T> void prim_irfftn2(int H, int W, int64_t P, const void *in, void *out) {
     const int64_t Wf = W / 2 + 1;
     DevBuf din(sizeof(cx<T>) * H * Wf * P), dout(sizeof(T) * H * W * P);
-    FftPlan pw, ph;
-    pw.init(W);
-    ph.init(H);
+    Plans pl(W, H);
+    const FftPlan &pw = pl.w, &ph = pl.h;
     SA_HIP(hipMemcpy(din.p, in, sizeof(cx<T>) * H * Wf * P, hipMemcpyHostToDevice));
     irfft2<T>(nullptr, pw, ph, din.as<cx<T>>(), din.as<cx<T>>(), dout.as<T>(), H, W, P);
     SA_HIP(hipDeviceSynchronize());
     SA_HIP(hipMemcpy(out, dout.p, sizeof(T) * H * W * P, hipMemcpyDeviceToHost));
-    pw.destroy();
-    ph.destroy();
 }
 
 // signal.tikhonov_filter on device arrays (csc_kernels.h has the elementwise pieces)
@@ -60,9 +69,8 @@ void prim_tikhonov_dev(int H, int W, int64_t P, const void *s, double lmbda, int
     const int Hp = H + 2 * npd, Wp = W + 2 * npd;
     const int64_t Wfp = Wp / 2 + 1;
     DevBuf sp(sizeof(T) * (size_t)Hp * Wp * P), spf(sizeof(cx<T>) * (size_t)Hp * Wfp * P);
-    FftPlan pw, ph;
-    pw.init(Wp);
-    ph.init(Hp);
+    Plans pl(Wp, Hp);
+    const FftPlan &pw = pl.w, &ph = pl.h;
     launch_sympad<T>(nullptr, static_cast<const T *>(s), sp.as<T>(), H, W, P, npd);
     rfft2<T>(nullptr, pw, ph, sp.as<T>(), nullptr, T(0), spf.as<cx<T>>(), Hp, Wp, P);
     launch_tikhonov_divide<T>(nullptr, spf.as<cx<T>>(), Hp, Wp, P, lmbda);
@@ -70,8 +78,6 @@ void prim_tikhonov_dev(int H, int W, int64_t P, const void *s, double lmbda, int
     launch_crop_highpass<T>(nullptr, sp.as<T>(), static_cast<const T *>(s), static_cast<T *>(slp),
                             static_cast<T *>(shp), H, W, P, npd);
     SA_HIP(hipDeviceSynchronize());
-    pw.destroy();
-    ph.destroy();
 }
 
 template <typename T>
@@ -98,9 +104,8 @@ void prim_fftconv_dev(int ha, int wa, const int64_t *da, const void *a, int hb, 
     DevBuf pada(sizeof(T) * (size_t)H * W * pa), padb(sizeof(T) * (size_t)H * W * pb);
     DevBuf af(sizeof(cx<T>) * (size_t)H * Wf * pa), bf(sizeof(cx<T>) * (size_t)H * Wf * pb);
     DevBuf of(sizeof(cx<T>) * (size_t)H * Wf * po), tmp(sizeof(T) * (size_t)H * W * po);
-    FftPlan pw, ph;
-    pw.init(W);
-    ph.init(H);
+    Plans pl(W, H);
+    const FftPlan &pw = pl.w, &ph = pl.h;
     launch_zeropad2<T>(nullptr, static_cast<const T *>(a), pada.as<T>(), ha, wa, H, W, pa);
     launch_zeropad2<T>(nullptr, static_cast<const T *>(b), padb.as<T>(), hb, wb, H, W, pb);
     rfft2<T>(nullptr, pw, ph, pada.as<T>(), nullptr, T(0), af.as<cx<T>>(), H, W, pa);
@@ -112,8 +117,6 @@ void prim_fftconv_dev(int ha, int wa, const int64_t *da, const void *a, int hb, 
     irfft2<T>(nullptr, pw, ph, of.as<cx<T>>(), of.as<cx<T>>(), dst, H, W, po);
     if (roll) launch_roll2<T>(nullptr, tmp.as<T>(), static_cast<T *>(out), H, W, po, oh, ow);
     SA_HIP(hipDeviceSynchronize());
-    pw.destroy();
-    ph.destroy();
 }
 
 template <typename T> void prim_axpby(int64_t n, double a, const void *x, double b, const void *y,

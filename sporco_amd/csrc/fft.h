@@ -102,10 +102,23 @@ void irfft2(hipStream_t st, const FftPlan &planW, const FftPlan &planH, const cx
 // K <= 64 with the tile in LDS, or K <= 256 in slabs of filters that fit (four passes then).  Returns the number of tiles.
 // (force_slab > 0: the test switch SPORCO_AMD_COLS_SM_FORCE_SLAB, read once per handle -- slabs of
 // that many filters even where the tile fits)
+// (form, optional: which kernel the call launched -- diagnostics, SPORCO_AMD_QUERY_COLS_SM_FORM)
+struct ColsSmForm {
+    int threads = 0;   // workgroup size
+    int us = 0;        // rows of solve operands a thread requests together (the kernel's US)
+    int big = 0;       // the instantiation with the 6-, 10- and 12-point butterflies
+    int slab = 0;      // filters per slab; 0: the whole tile in LDS
+    int packed() const { return threads | us << 12 | big << 16 | slab << 17; }
+};
 template <typename T> bool fft_cols_sm_supported(const FftPlan &plan, int K, int force_slab = 0);
 template <typename T>
 int64_t fft_cols_sm(hipStream_t st, const FftPlan &plan, cx<T> *xf, const cx<T> *df, const cx<T> *sf,
                     const T *gram, T rho, int Wf, int CN, int K, int W, bool want_obj, double *partials,
-                    int force_slab = 0);
+                    int force_slab = 0, ColsSmForm *form = nullptr);
+
+// Throws ("transform length too large ...") when lines of plan.n points do not fit the LDS of one
+// workgroup: the check every line transform makes at its launch, for a caller that wants the answer
+// before the first launch of a chain.
+template <typename T> void fft_require_line_fits(const FftPlan &plan);
 
 }  // namespace sporco_amd

@@ -1120,10 +1120,14 @@ int64_t fft_c2r_vpost(hipStream_t st, const FftPlan &plan, const cx<T> *in, int6
                     : launch_lines<T, MODE_C2R, true, 1>(st, plan, a, n_outer);
 }
 
+template <typename T> void fft_require_line_fits(const FftPlan &plan) { (void)pick_cfg<T>(plan.n, 1); }
+
 template <typename T>
 void rfft2(hipStream_t st, const FftPlan &planW, const FftPlan &planH, const T *in, const T *in2,
            T s2, cx<T> *out, int H, int W, int64_t P) {
     const int64_t Wf = W / 2 + 1;
+    fft_require_line_fits<T>(planW);      // (both passes, before the first one is launched)
+    fft_require_line_fits<T>(planH);
     fft_r2c<T>(st, planW, in, in2, s2, out, H, P, (int64_t)W * P, P, Wf * P, P, 0, 0, 0);
     // columns: (wf, p) is one contiguous run of Wf*P complex columns per row h
     fft_c2c<T>(st, planH, false, out, out, 1, Wf * P, 0, Wf * P, 0, Wf * P, T(1));
@@ -1133,6 +1137,8 @@ template <typename T>
 void irfft2(hipStream_t st, const FftPlan &planW, const FftPlan &planH, const cx<T> *in,
             cx<T> *tmp, T *out, int H, int W, int64_t P) {
     const int64_t Wf = W / 2 + 1;
+    fft_require_line_fits<T>(planW);
+    fft_require_line_fits<T>(planH);
     fft_c2c<T>(st, planH, true, in, tmp, 1, Wf * P, 0, Wf * P, 0, Wf * P, T(1));
     fft_c2r<T>(st, planW, tmp, out, H, P, Wf * P, P, (int64_t)W * P, P,
                T(1.0 / ((double)H * (double)W)), 0, 0);
@@ -1170,7 +1176,7 @@ template <typename T> bool fft_cols_sm_supported(const FftPlan &plan, int K, int
 template <typename T>
 int64_t fft_cols_sm(hipStream_t st, const FftPlan &plan, cx<T> *xf, const cx<T> *df, const cx<T> *sf,
                     const T *gram, T rho, int Wf, int CN, int K, int W, bool want_obj, double *partials,
-                    int force_slab) {
+                    int force_slab, ColsSmForm *form) {
     SA_REQUIRE(fft_cols_sm_supported<T>(plan, K, force_slab), "fft_cols_sm: unsupported length / filter count");
     ColsSmArgs<T> a{};
     a.xf = xf;
@@ -1191,7 +1197,7 @@ int64_t fft_cols_sm(hipStream_t st, const FftPlan &plan, cx<T> *xf, const cx<T> 
     for (int i = 0; i < plan.nrad_ip; ++i) a.radix[i] = plan.radix_ip[i];
     a.want_obj = want_obj ? 1 : 0;
     a.partials = partials;
-    bool big = false;       // (a 10-, 12-, 14- or 15-point pass: the instantiations that carry them)
+    bool big = false;       // (a 6-, 10- or 12-point pass: the instantiations that carry them)
     for (int i = 0; i < plan.nrad_ip; ++i) big = big || plan.radix_ip[i] == 6 || plan.radix_ip[i] >= 10;
     static PerDeviceOnce attr_set;
     if (!(K <= 64 && cols_sm_lds<T>(plan.n, K) <= kLdsBudget) || force_slab > 0) {
@@ -1213,6 +1219,12 @@ int64_t fft_cols_sm(hipStream_t st, const FftPlan &plan, cx<T> *xf, const cx<T> 
             hipLaunchKernelGGL((cols_sm_slab_kernel<T, false>), sgrid, dim3(1024), cols_sm_slab_lds<T>(plan.n, a.Ks),
                                st, a);
         SA_HIP(hipGetLastError());
+        if (form) {
+            form->threads = 1024;
+            form->us = 4;
+            form->big = big ? 1 : 0;
+            form->slab = a.Ks;
+        }
         return tiles;
     }
     const size_t lds = cols_sm_lds<T>(plan.n, K);
@@ -1233,15 +1245,27 @@ int64_t fft_cols_sm(hipStream_t st, const FftPlan &plan, cx<T> *xf, const cx<T> 
     // rows per thread: all operands in one batch while the registers allow it
     const int nit = (int)ceil_div(plan.n, threads / a.Kp);
     constexpr int UMAX = sizeof(T) == 8 ? 6 : 12;
-    if (big)       // (the wide butterflies leave no registers for a long operand batch)
+    int us;
+    if (big) {     // (the wide butterflies leave no registers for a long operand batch)
+        us = UMAX / 3;
         hipLaunchKernelGGL((cols_sm_kernel<T, UMAX / 3, true>), dim3(grid), dim3(threads), lds, st, a);
-    else if (nit <= UMAX / 3)
+    } else if (nit <= UMAX / 3) {
+        us = UMAX / 3;
         hipLaunchKernelGGL((cols_sm_kernel<T, UMAX / 3>), dim3(grid), dim3(threads), lds, st, a);
-    else if (nit <= 2 * UMAX / 3 || nit > UMAX)
+    } else if (nit <= 2 * UMAX / 3 || nit > UMAX) {
+        us = 2 * UMAX / 3;
         hipLaunchKernelGGL((cols_sm_kernel<T, 2 * UMAX / 3>), dim3(grid), dim3(threads), lds, st, a);
-    else
+    } else {
+        us = UMAX;
         hipLaunchKernelGGL((cols_sm_kernel<T, UMAX>), dim3(grid), dim3(threads), lds, st, a);
+    }
     SA_HIP(hipGetLastError());
+    if (form) {
+        form->threads = threads;
+        form->us = us;
+        form->big = big ? 1 : 0;
+        form->slab = 0;
+    }
     return tiles;
 }
 
@@ -1259,7 +1283,9 @@ int64_t fft_cols_sm(hipStream_t st, const FftPlan &plan, cx<T> *xf, const cx<T> 
                                       int64_t, T, const PostParams<T> &, cx<T> *, int64_t, int64_t, double *); \
     template bool fft_cols_sm_supported<T>(const FftPlan &, int, int);                          \
     template int64_t fft_cols_sm<T>(hipStream_t, const FftPlan &, cx<T> *, const cx<T> *,        \
-                                    const cx<T> *, const T *, T, int, int, int, int, bool, double *, int); \
+                                    const cx<T> *, const T *, T, int, int, int, int, bool, double *, int, \
+                                    ColsSmForm *);                                               \
+    template void fft_require_line_fits<T>(const FftPlan &);                                     \
     template void rfft2<T>(hipStream_t, const FftPlan &, const FftPlan &, const T *, const T *,  \
                            T, cx<T> *, int, int, int64_t);                                       \
     template void irfft2<T>(hipStream_t, const FftPlan &, const FftPlan &, const cx<T> *,        \
