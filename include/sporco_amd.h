@@ -385,6 +385,10 @@ typedef struct {
 #define SPORCO_AMD_OUT_CGIT 13   /* CG D-step: scipy's cg() status, 0 = converged, else MaxIter
                                     (what the reference records as XSlvCGIt, linalg.py:578) */
 #define SPORCO_AMD_OUT_CGN 14    /* CG D-step: iterations actually run                     */
+#define SPORCO_AMD_OUT_SN2 14    /* l1l1_iter: Parseval sum of |A^T u|^2 / (H W) (the slot of CGN, which
+                                    no sparse coding call fills)                            */
+#define SPORCO_AMD_OUT_RGRX 15   /* l1l1_iter: what OUT_RGR is to ConvBPDNGradReg -- the two-block
+                                    classes keep block 0's |AXnr|^2 in OUT_RGR                */
 #define SPORCO_AMD_OUT_COUNT 16
 
 /* One full ADMM iteration on device: xstep (cbpdn.py:267-281: rfftn(Y-U),
@@ -672,6 +676,19 @@ int sporco_amd_csc_mdcpl_init(sporco_amd_csc_t h, const void *S);
  * DFID = |W g0|^2 (twice the data fidelity, :2262-2268), L1 = |wl1 g1|_1; XRRS sums. */
 int sporco_amd_csc_mdcpl_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
                               double out[SPORCO_AMD_OUT_COUNT]);
+
+/* ---- l1 data fidelity with l1 and gradient regularisation: sporco.admm.cbpdn.ConvL1L1Grd
+ * (cbpdn.py:2488-2774) on the state of the mask-decoupling calls above (sporco_amd_csc_mdcpl_init;
+ * mask, L1Weight and GradWeight through set_data_mask / set_l1_weight / set_grad_weight).
+ * One iteration.  params as for mdcpl_iter plus mu (SPORCO_AMD_FLAG_GRADREG is accepted and implied).
+ * xstep (:2676-2699): (D^H D + (mu / rho) Wgrd GHG + I) x = D^H (y0 - u0 + s) + y1 - u1; ystep
+ * (:2716-2726): y0 = soft(AX0 + u0 - s, W / rho), y1 as for mdcpl_iter; ustep.  out as for mdcpl_iter,
+ * except: DFID = sum |W g0| (the data fidelity itself, :2744-2749); RGRX = Parseval sum of GradWeight
+ * GHGf |Xf|^2 / (H W) (twice RegGrad); S2 = |A^T (Yprev - Y)|^2 and SN2 = |A^T u|^2, A^T v =
+ * irfftn(conj(Df) rfftn(v0)) + v1 (:2753-2763), both with SPORCO_AMD_FLAG_RESID only.  Generic
+ * transforms on every shape; single- and multi-channel dictionaries (at most 8 channels). */
+int sporco_amd_csc_l1l1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]);
 
 /* ---- ADMM with inhibition: sporco.admm.cbpdnin.ConvBPDNInhib (cbpdnin.py:28-352) -------------
  * The iteration is the ConvBPDN one (sporco_amd_csc_admm_iter, or the staged calls) with an array

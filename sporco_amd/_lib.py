@@ -55,6 +55,7 @@ OUT_XRRS_D2, OUT_XRRS_AX2, OUT_XRRS_B2 = 8, 9, 10
 OUT_RGR = 11
 OUT_CNSTR = 12
 OUT_CGIT, OUT_CGN = 13, 14
+OUT_SN2, OUT_RGRX = 14, 15      # l1l1_iter: |A^T u|^2, and RegGrad's sum beside block 0's use of OUT_RGR
 OUT_COUNT = 16
 
 PGM_F, PGM_DFID, PGM_L1, PGM_HESS, PGM_RSDL, PGM_FY, PGM_LIN, PGM_DXY2 = range(8)
@@ -82,7 +83,7 @@ EXPORTS = (
     'sporco_amd_csc_ccmod_getdict', 'sporco_amd_csc_setdict_from_dstep', 'sporco_amd_csc_asum',
     'sporco_amd_csc_set_filter_sizes', 'sporco_amd_csc_cns_init', 'sporco_amd_csc_cns_iter', 'sporco_amd_csc_cns_md_init', 'sporco_amd_csc_cns_mean_ptr',
     'sporco_amd_csc_dstep_init', 'sporco_amd_csc_dstep_iter', 'sporco_amd_csc_ccmod_sgd_step',
-    'sporco_amd_csc_mdcpl_init', 'sporco_amd_csc_mdcpl_iter', 'sporco_amd_csc_dstep_md_init',
+    'sporco_amd_csc_mdcpl_init', 'sporco_amd_csc_mdcpl_iter', 'sporco_amd_csc_l1l1_iter', 'sporco_amd_csc_dstep_md_init',
     'sporco_amd_csc_set_data_mask', 'sporco_amd_csc_masked_grad',
     'sporco_amd_csc_inhib_setup', 'sporco_amd_csc_inhib_update',
     'sporco_amd_csc_tv_setup', 'sporco_amd_csc_tv_xstep', 'sporco_amd_csc_tv_ystep', 'sporco_amd_csc_tv_adjoint',
@@ -315,6 +316,7 @@ def load(path=None):
         'sporco_amd_csc_pd_dfid': [vp, i32, dptr],
         'sporco_amd_csc_pd_reconstruct': [vp, i32, vp],
         'sporco_amd_csc_mdcpl_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_l1l1_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_dstep_init': [vp, vp],
         'sporco_amd_csc_dstep_md_init': [vp, vp, vp],
         'sporco_amd_csc_dstep_iter': [vp, ctypes.POINTER(DstepParams), dptr],
@@ -694,6 +696,13 @@ class Solver(object):
     def mdcpl_iter(self, params):
         out = self._out()
         check(self._lib.sporco_amd_csc_mdcpl_iter(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def l1l1_iter(self, params):
+        """One iteration of ConvL1L1Grd on the mask-decoupling state (sporco_amd_csc_l1l1_iter);
+        ``params.mu`` carries mu.  Returns the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_l1l1_iter(self._h, ctypes.byref(params), out))
         return list(out)
 
     def inhib_setup(self, Wg, taps_rows, taps_cols, want_self, lmbda):

@@ -30,7 +30,7 @@ from .. import cnvrep as cr
 from ..fft import complex_dtype, real_dtype
 
 __all__ = ['GenericConvBPDN', 'ConvBPDN', 'ConvBPDNJoint', 'ConvBPDNGradReg',
-           'ConvBPDNMaskDcpl', 'AddMaskSim']
+           'ConvBPDNMaskDcpl', 'ConvL1L1Grd', 'AddMaskSim']
 
 
 class _DeviceArray(object):
@@ -1103,7 +1103,7 @@ class ConvBPDNMaskDcpl(ConvBPDN):
         if self.opt['LinSolveCheck']:
             flags |= _lib.FLAG_XRRS
         p.flags = flags
-        self._sums = self._dev.mdcpl_iter(p)
+        self._sums = self._device_iteration(p)
         if self._reducer is not None:
             self._sums = self._reducer.sum(self._sums)
         self._u_scale = 1.0
@@ -1115,6 +1115,10 @@ class ConvBPDNMaskDcpl(ConvBPDN):
         res = self.compute_residuals()
         self.timer.start('solve_wo_rsdl')
         return res
+
+    def _device_iteration(self, p):
+        """The one device call of an iteration; returns the sums."""
+        return self._dev.mdcpl_iter(p)
 
     def residual_norms(self):
         """admm.py:1404-1437 with the dual residual of cbpdn.py:1814-1824."""
@@ -1138,6 +1142,116 @@ class ConvBPDNMaskDcpl(ConvBPDN):
         if X is None:
             return self._dev.reconstruct(_lib.VAR_X)[..., 0]
         return super(ConvBPDNMaskDcpl, self).reconstruct(X)
+
+
+class ConvL1L1Grd(ConvBPDNMaskDcpl):
+    r"""Convolutional sparse coding with an l1 data fidelity term under a mask, an l1 penalty on the
+    coefficient maps and an l2 penalty on their gradient: minimise
+    ||W(sum_m d_m * x_m - s)||_1 + lambda sum_m ||x_m||_1 + (mu/2) sum_i sum_m w_m ||G_i x_m||_2^2
+    through the two-block constraint of :class:`ConvBPDNMaskDcpl` (reference class:
+    sporco/admm/cbpdn.py:2488-2774) -- the reference's model for impulse noise.
+
+    One iteration is one call of ``sporco_amd_csc_l1l1_iter`` (csrc/csc_l1l1.h): the x step is the
+    gradient-regularised solve of :class:`ConvBPDNGradReg` with rho = 1 and mu / rho in mu's place
+    (iterated Sherman-Morrison for a multi-channel dictionary), block 1 the ConvBPDN epilogue, block 0
+    a soft threshold by W / rho, and the dual residual is this class's own, rho ||A^T (Yprev - Y)||
+    against rho ||A^T U|| (:2753-2763).  The generic transforms serve every shape.
+
+    In scope: ``dimN = 2``, float32 / float64, ``dimK`` 0 / 1, multi-channel signals and dictionaries,
+    ``W``, scalar or array ``L1Weight``, scalar or per-filter ``GradWeight``, ``NonNegCoef``,
+    ``NoBndryCross``, ``AutoRho`` (off by default), ``RelaxParam``, ``AuxVarObj``, ``LinSolveCheck``,
+    ``Y0`` / ``U0`` (concatenated blocks), ``ReturnVar``, ``setdict``.  ``HighMemSolve`` is accepted and
+    has no effect.  Refused with ``NotImplementedError``: ``dimN`` 1 / 3, complex data, ``reducer=``,
+    resident or device-array inputs, pickling.
+
+    IterationStats fields: ``Iter, ObjFun, DFid, RegL1, RegGrad, PrimalRsdl, DualRsdl, EpsPrimal,
+    EpsDual, Rho, XSlvRelRes, Time``.  ``DFid`` is the l1 sum itself (no factor 1/2), ``RegGrad``
+    always comes from ``Xf``, ``RegL1`` is evaluated at X, or at Y1 under ``AuxVarObj``.
+    """
+
+    class Options(ConvBPDNMaskDcpl.Options):
+        """Adds ``GradWeight``: scalar, or one weight per filter (cbpdn.py:2564-2595)."""
+
+        defaults = copy.deepcopy(ConvBPDNMaskDcpl.Options.defaults)
+        defaults.update({'GradWeight': 1.0})
+
+        def __init__(self, opt=None):
+            ConvBPDNMaskDcpl.Options.__init__(self, {} if opt is None else opt)
+
+    itstat_fields_objfn = ('ObjFun', 'DFid', 'RegL1', 'RegGrad')
+    hdrtxt_objfn = ('Fnc', 'DFid', u'Regℓ1', u'Regℓ2∇')
+    hdrval_objfun = {'Fnc': 'ObjFun', 'DFid': 'DFid', u'Regℓ1': 'RegL1', u'Regℓ2∇': 'RegGrad'}
+
+    GHGf = ConvBPDNGradReg.GHGf
+
+    def __init__(self, D, S, lmbda, mu, W=None, opt=None, dimK=None, dimN=2, **backend):
+        name = type(self).__name__
+        if opt is None:
+            opt = ConvL1L1Grd.Options()
+        if dimN != 2:
+            raise NotImplementedError("%s: dimN = 2 (images); the gradient term is the "
+                                      "two-dimensional one" % name)
+        if backend.get('reducer') is not None:
+            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
+        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, S)):
+            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
+        if np.iscomplexobj(D) or np.iscomplexobj(S):
+            raise NotImplementedError("%s handles real-valued D and S" % name)
+        self.set_dtype(opt, S.dtype)
+        self.mu = self.dtype.type(mu)
+        gw = opt['GradWeight']
+        if hasattr(gw, 'ndim') and np.ndim(gw) > 0:
+            # one weight per filter, broadcast along the filter axis (cbpdn.py:2649-2653)
+            self.Wgrd = np.asarray(np.asarray(gw).reshape((1,) * (dimN + 2) + np.shape(gw)),
+                                   dtype=self.dtype)
+        else:
+            self.Wgrd = np.asarray(gw, dtype=self.dtype)
+        super(ConvL1L1Grd, self).__init__(D, S, lmbda, W, opt, dimK=dimK, dimN=dimN, **backend)
+
+    def _upload_weights(self):
+        super(ConvL1L1Grd, self)._upload_weights()
+        if self.Wgrd.size == 1:
+            self._wg_scalar = float(self.Wgrd.ravel()[0])
+            self._dev.set_grad_weight(None)
+        else:
+            if self.Wgrd.size != self.cri.M:
+                raise ValueError("GradWeight must be a scalar or hold one weight per filter")
+            self._wg_scalar = 1.0
+            self._dev.set_grad_weight(self.Wgrd.ravel())
+
+    def _mu_eff(self):
+        # a scalar GradWeight folds into mu: mu * (w GHGf)
+        return float(self.mu) * self._wg_scalar
+
+    def __getstate__(self):
+        raise NotImplementedError("%s: pickling is not offered" % type(self).__name__)
+
+    def _device_iteration(self, p):
+        p.flags |= _lib.FLAG_GRADREG
+        return self._dev.l1l1_iter(p)
+
+    def residual_norms(self):
+        """admm.py:1404-1437 with the dual residual of cbpdn.py:2753-2763: both norms are those of
+        A^T applied to a two-block array, summed on the device in the frequency domain."""
+        s = self._sums
+        rho = float(self.rho)
+        nr = np.sqrt(s[_lib.OUT_R2] + s[_lib.OUT_L21])
+        ns = rho * np.sqrt(s[_lib.OUT_S2])
+        rn = max(np.sqrt(s[_lib.OUT_AX2] + s[_lib.OUT_RGR]),
+                 np.sqrt(s[_lib.OUT_Y2] + s[_lib.OUT_CNSTR]), self._nrm_c)
+        sn = rho * np.sqrt(s[_lib.OUT_SN2])
+        return nr, ns, rn, sn
+
+    def eval_objfn(self):
+        """||W g0||_1 + lmbda ||wl1 g1||_1 + (mu/2) sum_i ||Wgrd^(1/2) G_i x||^2 (cbpdn.py:2730-2749)."""
+        g0v = self._sums[_lib.OUT_DFID]
+        g1v = abs(self._wl1_scalar) * self._sums[_lib.OUT_L1]
+        rgr = self._wg_scalar * self._sums[_lib.OUT_RGRX] / 2.0
+        return (g0v + self.lmbda * g1v + self.mu * rgr, g0v, g1v, rgr)
+
+    def rhochange(self):
+        """Nothing is cached on the host: the x step forms mu / rho itself (the tables of the
+        multi-channel solve are rebuilt on the device when it moves)."""
 
 
 class AddMaskSim(object):

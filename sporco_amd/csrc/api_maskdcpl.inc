@@ -183,10 +183,12 @@
                 SA_HIP(hipMalloc((void **)&ism_mm, sizeof(cx<T>) * npix * Cd * Cd));
             }
             ProfScope ps(prof, PS_SM_SOLVE);
-            if (!ism_valid || ism_rho != 1.0) {
+            // (ism_mu: tables left by a gradient-regularised solve on this handle are not these)
+            if (!ism_valid || ism_rho != 1.0 || ism_mu != -1.0) {
                 launch_ism_setup<T>(st, Df, ism_gam, ism_del, ism_mm, npix, Cd, K, T(1));
                 ism_valid = true;
                 ism_rho = 1.0;
+                ism_mu = -1.0;
             }
             nb = launch_ism_solve<T>(st, Vf, Xf, Df, innerb, ism_gam, ism_del, ism_mm, T(1), npix, Cd,
                                      N, K, W, false, xr, part_a);

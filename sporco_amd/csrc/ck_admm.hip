@@ -526,9 +526,16 @@ __global__ void __launch_bounds__(kThreads) admm_post_kernel(const PostParams<T>
             yv = reinterpret_cast<const Vec<T, VEC> *>(p.y)[i];
             uv = reinterpret_cast<const Vec<T, VEC> *>(p.u)[i];
         }
+        const Vec<T, VEC> yo = yv;
 #pragma unroll
         for (int e = 0; e < VEC; ++e)
             admm_post_elem<T, GENERAL>(p, i * VEC + e, P, xv.v[e], yv.v[e], uv.v[e], acc, &vv.v[e]);
+        if (p.dy_out) {
+            Vec<T, VEC> dv;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) dv.v[e] = yo.v[e] - yv.v[e];
+            reinterpret_cast<Vec<T, VEC> *>(p.dy_out)[i] = dv;
+        }
         if (!GENERAL && p.v_out) {
             reinterpret_cast<Vec<T, VEC> *>(p.v_out)[i] = vv;
         } else {
@@ -697,6 +704,7 @@ static int launch_post_joint_reg(hipStream_t st, const PostParams<T> &p, double 
 }
 
 template <typename T> int launch_admm_post(hipStream_t st, const PostParams<T> &p, double *partials) {
+    SA_REQUIRE(!p.dy_out || !((p.flags & F_JOINT) || p.v_in || p.v_out), "admm_post: dy_out goes with the plain (Y, U) form");
     const int64_t E = (int64_t)p.d.H * p.d.W * p.d.C * p.d.N * p.d.K;
     const size_t lds = sizeof(double) * 8 * (kThreads / kWave);
     int grid;

@@ -28,7 +28,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "fft_c2r_vpost",    "fft_c2r_vpost_emit",
                                     "inhib_update",     "tv_ystep",         "tv_adjoint",
                                     "rtv_solve",        "rtv_ystep",        "rtv_dual",
-                                    "pd_solve",         "pd_recon"};
+                                    "pd_solve",         "pd_recon",
+                                    "l1l1_y0step",      "l1l1_dual"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -435,6 +436,7 @@ template <typename T> struct Csc : CscBase {
         tv_release();
         rtv_release();
         pd_release();
+        l1l1_release();
         big_free(gemit);
         if (part_vpost) (void)hipFree(part_vpost);
         big_free(cols_out[0]);
@@ -631,6 +633,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_tv.inc"
 #include "api_rtv.inc"
 #include "api_pd.inc"
+#include "api_l1l1.inc"
 };
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

@@ -17,6 +17,7 @@
 #include "csc_fused.h"
 #include "csc_inhib.h"
 #include "csc_kernels.h"
+#include "csc_l1l1.h"
 #include "csc_pd.h"
 #include "csc_pgm.h"
 #include "csc_rows.h"
@@ -96,6 +97,8 @@ enum ProfSlot {
     PS_RTV_DUAL,                // ... the adjoint maps and the frequency-domain residual norms
     PS_PD_SOLVE,                // ConvProdDictBPDN: the eigen-channel rank-one x step solve (csc_pd.h)
     PS_PD_RECON,                // ... the reconstruction spectrum through B (reconstruct, fidelity at Y)
+    PS_L1L1_Y0STEP,             // ConvL1L1Grd: relax + soft threshold + u step of block 0 (csc_l1l1.h)
+    PS_L1L1_DUAL,               // ... both dual-residual norms in one read pass
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -220,6 +223,7 @@ struct CscBase {
     virtual void *cns_mean_ptr(int64_t *count) = 0;
     virtual void mdcpl_init(const void *S) = 0;
     virtual void mdcpl_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void l1l1_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void dstep_init(const void *Y0) = 0;
     virtual void dstep_md_init(const void *Y0, const void *S) = 0;
     virtual void dstep_iter(const sporco_amd_dstep_params &p, double *out_dev) = 0;

@@ -113,6 +113,9 @@ template <typename T> struct PostParams {
     const T *v_in = nullptr;
     T *v_out = nullptr;
     T thr_prev = T(0);
+    // dy_out, when set, receives Yprev - Y (the (Y, U) form of the streaming epilogue kernel only:
+    // the dual residual of ConvL1L1Grd, csc_l1l1.h); nothing else changes with it
+    T *dy_out = nullptr;
 };
 template <typename T> int launch_admm_post(hipStream_t st, const PostParams<T> &p, double *partials);
 
