@@ -41,6 +41,7 @@
  *   SPORCO_AMD_COLS_SM_FORCE_SLAB=k   (tests) ... in slabs of k filters even where the tile fits
  *   SPORCO_AMD_MD_GENERIC=1     ConvBPDNMaskDcpl on the generic chain
  *   SPORCO_AMD_CNS_GENERIC=1    consensus dictionary update on the generic chain
+ *   SPORCO_AMD_PDL1_GENERIC=1   (tests) pdl1_solve in its one-thread-per-system form on every shape
  *   SPORCO_AMD_CG_HOST=1        CG dictionary update: the scalars read back every iteration
  *   SPORCO_AMD_PLACEMENT=0|force   no placement search for concurrently written arrays / the search
  *                               (and the striped column output) also for small arrays -- tests
@@ -214,6 +215,8 @@ int sporco_amd_csc_stream(sporco_amd_csc_t h, void **stream);
                                           * 6-, 10- and 12-point butterflies; bits 17 and up: filters
                                           * per slab, 0 when the whole tile fits LDS -- diagnostics, so
                                           * that a test can tell which instantiation it exercised */
+#define SPORCO_AMD_QUERY_PDL1_WAVE_LAUNCHES 10     /* as PD_WAVE_LAUNCHES / PD_GENERIC_LAUNCHES, for the  */
+#define SPORCO_AMD_QUERY_PDL1_GENERIC_LAUNCHES 11  /* pdl1_solve launches of sporco_amd_csc_pdl1_iter      */
 int sporco_amd_csc_query(sporco_amd_csc_t h, int what, int *out);
 /* Diagnostics, no reference counterpart: where the handle put the X-sized arrays that one kernel
  * writes at the same time (the spectrum buffer T and the iterate buffers of the fused ADMM
@@ -387,6 +390,8 @@ typedef struct {
 #define SPORCO_AMD_OUT_CGN 14    /* CG D-step: iterations actually run                     */
 #define SPORCO_AMD_OUT_SN2 14    /* l1l1_iter: Parseval sum of |A^T u|^2 / (H W) (the slot of CGN, which
                                     no sparse coding call fills)                            */
+#define SPORCO_AMD_OUT_R02 14    /* pdl1_iter: block 0's |AXnr - y0 - s|^2 (l1l1_iter keeps it in OUT_L21, which
+                                    the joint class needs for its l2,1 sum)                 */
 #define SPORCO_AMD_OUT_RGRX 15   /* l1l1_iter: what OUT_RGR is to ConvBPDNGradReg -- the two-block
                                     classes keep block 0's |AXnr|^2 in OUT_RGR                */
 #define SPORCO_AMD_OUT_COUNT 16
@@ -827,6 +832,33 @@ int sporco_amd_csc_pd_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
 int sporco_amd_csc_pd_dfid(sporco_amd_csc_t h, int var, double out[SPORCO_AMD_OUT_COUNT]);
 /* out (H, W, cs, N) = irfftn(B sum_m Df_m rfftn(var)_m), host memory. */
 int sporco_amd_csc_pd_reconstruct(sporco_amd_csc_t h, int var, void *out);
+
+/* ---- product dictionary with l1 data fidelity and gradient regularisation:
+ * sporco.admm.pdcsc.ConvProdDictL1L1Grd / ConvProdDictL1L1GrdJoint (pdcsc.py:293-701) on a handle as for
+ * the pd calls above (C = Cb channels, single-channel dictionary; L1Weight and GradWeight through
+ * set_l1_weight / set_grad_weight).  The two-block constraint is y0 = D X B^T - S (cs channels), y1 = X:
+ * block 1 lives in VAR_Y / VAR_U, block 0 in buffers of cs N planes that the handle owns.
+ * sporco_amd_csc_pdl1_setup: what sporco_amd_csc_pd_setup does, plus the mask (NULL: none; else an array
+ * (H, W, cs, N) of the handle's dtype) and block 0, which the first call creates at zero and a later
+ * call keeps (a change of B or S between two solves).  sporco_amd_csc_pd_reconstruct serves these
+ * classes too. */
+int sporco_amd_csc_pdl1_setup(sporco_amd_csc_t h, const double *B, const double *Q, const double *gamma,
+                              const void *S, int32_t cs, const void *mask);
+/* Host copy of block 0: which = 0 (y0) or 1 (u0, without a pending u_scale), (H, W, cs, N); upload != 0
+ * writes the device array from `buf`, else `buf` receives it. */
+int sporco_amd_csc_pdl1_block0(sporco_amd_csc_t h, int32_t which, int32_t upload, void *buf);
+/* One iteration.  params as for l1l1_iter; with SPORCO_AMD_FLAG_JOINT block 1 is the l2,1 shrinkage over
+ * the channel axis with threshold lmbda / rho and no l1 term (prox_sl1l2(., 0, .), :681-692).
+ * xstep (:509-540): per eigen-channel c' of B^T B = Q Gamma Q^T, (gamma_c' conj(d) d^T + diag(1 + (mu / rho)
+ * Wgrd GHG)) xh_c' = conj(d) ((BQ)^T z0)_c' + (Q^T z1)_c', x = Q xh (profile slot "pdl1_solve"), which also
+ * writes the block-0 constraint spectrum (BQ)(d . xh); then the block steps of l1l1_iter.  out as for
+ * l1l1_iter, except: block 0's |AXnr - y0 - s|^2 is in R02; L21 = the l2,1 sum (FLAG_JOINT); S2 = the
+ * Parseval sum of |B^T conj(Df) rfftn(u0) + rfftn(u1)|^2 / (H W) at the new u (this class's dual
+ * residual, :568-571; profile slot "pdl1_dual"; FLAG_RESID only) and no SN2: sn = rho ||u|| is U2 + CGIT.
+ * The XRRS sums are those of the reference's check (:530-538) in eigen-coordinates.  Generic transforms
+ * on every shape. */
+int sporco_amd_csc_pdl1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]);
 
 /* ---- online dictionary learning (sporco.dictlrn.onlinecdl.OnlineConvBPDNDictLearn.dstep,
  * onlinecdl.py:310-333) -------------------------------------------------------------------

@@ -43,6 +43,7 @@ QUERY_FUSED_COLS, QUERY_FUSED_ROWS, QUERY_FUSED_PGM, QUERY_DEVICE_FILTERS, QUERY
 QUERY_PERSIST_RUNS = 5
 QUERY_CCMOD_GROUPS = 6
 QUERY_PD_WAVE_LAUNCHES, QUERY_PD_GENERIC_LAUNCHES = 7, 8
+QUERY_PDL1_WAVE_LAUNCHES, QUERY_PDL1_GENERIC_LAUNCHES = 10, 11
 QUERY_COLS_SM_FORM = 9
 HINT_KEEP_VFORM = 0
 HINT_ONE_LAUNCH = 1
@@ -55,6 +56,7 @@ OUT_XRRS_D2, OUT_XRRS_AX2, OUT_XRRS_B2 = 8, 9, 10
 OUT_RGR = 11
 OUT_CNSTR = 12
 OUT_CGIT, OUT_CGN = 13, 14
+OUT_R02 = 14                   # pdl1_iter: block 0's |AXnr - y0 - s|^2
 OUT_SN2, OUT_RGRX = 14, 15      # l1l1_iter: |A^T u|^2, and RegGrad's sum beside block 0's use of OUT_RGR
 OUT_COUNT = 16
 
@@ -89,6 +91,7 @@ EXPORTS = (
     'sporco_amd_csc_tv_setup', 'sporco_amd_csc_tv_xstep', 'sporco_amd_csc_tv_ystep', 'sporco_amd_csc_tv_adjoint',
     'sporco_amd_csc_rtv_setup', 'sporco_amd_csc_rtv_xstep', 'sporco_amd_csc_rtv_ystep', 'sporco_amd_csc_rtv_dual',
     'sporco_amd_csc_pd_setup', 'sporco_amd_csc_pd_xstep', 'sporco_amd_csc_pd_dfid', 'sporco_amd_csc_pd_reconstruct',
+    'sporco_amd_csc_pdl1_setup', 'sporco_amd_csc_pdl1_block0', 'sporco_amd_csc_pdl1_iter',
     'sporco_amd_csc_profile', 'sporco_amd_csc_profile_read', 'sporco_amd_profile_slots',
     'sporco_amd_dev_malloc', 'sporco_amd_dev_free', 'sporco_amd_dev_upload',
     'sporco_amd_dev_download', 'sporco_amd_dev_axpby', 'sporco_amd_tikhonov_filter_dev',
@@ -315,6 +318,9 @@ def load(path=None):
         'sporco_amd_csc_pd_xstep': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_pd_dfid': [vp, i32, dptr],
         'sporco_amd_csc_pd_reconstruct': [vp, i32, vp],
+        'sporco_amd_csc_pdl1_setup': [vp, dptr, dptr, dptr, vp, i32, vp],
+        'sporco_amd_csc_pdl1_block0': [vp, i32, i32, vp],
+        'sporco_amd_csc_pdl1_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_mdcpl_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_l1l1_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_dstep_init': [vp, vp],
@@ -818,6 +824,45 @@ class Solver(object):
         out = np.empty((H, W, self.pd_Cs, N), dtype=self.dtype)
         check(self._lib.sporco_amd_csc_pd_reconstruct(self._h, int(var), _ptr(out)))
         return out
+
+    def pdl1_setup(self, B, Q, gamma, S, mask=None):
+        """State of ConvProdDictL1L1Grd (sporco_amd_csc_pdl1_setup): the arguments of :meth:`pd_setup` and
+        the mask, ``None`` or an array that broadcasts against ``S`` (H, W, Cs, N).  Block 0 of Y and U is
+        created at zero by the first call and kept by later ones."""
+        H, W, Cb, N, K = self.dims
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64).ravel()
+        if B.ndim != 2 or B.shape[1] != Cb or Q.shape != (Cb, Cb) or gamma.size != Cb:
+            raise ValueError("B must be (Cs, %d), Q (%d, %d) and gamma hold %d values" % (Cb, Cb, Cb, Cb))
+        self.pd_Cs = int(B.shape[0])
+        shp = (H, W, self.pd_Cs, N)
+        S = _carr(S, self.dtype).reshape(shp)
+        if mask is not None:
+            mask = _carr(np.broadcast_to(np.asarray(mask, dtype=self.dtype), shp), self.dtype)
+        dp = ctypes.POINTER(ctypes.c_double)
+        check(self._lib.sporco_amd_csc_pdl1_setup(self._h, B.ctypes.data_as(dp), Q.ctypes.data_as(dp),
+                                                  gamma.ctypes.data_as(dp), _ptr(S), self.pd_Cs,
+                                                  None if mask is None else _ptr(mask)))
+
+    def pdl1_block0(self, which, value=None):
+        """Block 0 of Y (``which`` 0) or U (1), (H, W, Cs, N, 1): returned, or with ``value`` uploaded
+        (sporco_amd_csc_pdl1_block0)."""
+        H, W, Cb, N, K = self.dims
+        shp = (H, W, self.pd_Cs, N, 1)
+        if value is None:
+            out = np.empty(shp, dtype=self.dtype)
+            check(self._lib.sporco_amd_csc_pdl1_block0(self._h, int(which), 0, _ptr(out)))
+            return out
+        value = _carr(value, self.dtype).reshape(shp)
+        check(self._lib.sporco_amd_csc_pdl1_block0(self._h, int(which), 1, _ptr(value)))
+
+    def pdl1_iter(self, params):
+        """One iteration of ConvProdDictL1L1Grd / ConvProdDictL1L1GrdJoint (sporco_amd_csc_pdl1_iter);
+        returns the sums."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_pdl1_iter(self._h, ctypes.byref(params), out))
+        return list(out)
 
     def admm_iter_dev(self, params, out_dev_ptr):
         check(self._lib.sporco_amd_csc_admm_iter_dev(self._h, ctypes.byref(params),

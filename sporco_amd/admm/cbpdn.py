@@ -973,7 +973,7 @@ class ConvBPDNMaskDcpl(ConvBPDN):
         shp = (1,) * 5 if W.size == 1 else cr.mskWshape(W, self.cri)
         self.W = np.asarray(W.reshape(shp), dtype=self.dtype)
         self._upload_weights()
-        self._dev.mdcpl_init(self.S)
+        self._init_blocks()
         # warm start (admm.py:262-272): Y0 / U0 are the concatenated [block 0; block 1] arrays
         # of ADMMTwoBlockCnstrnt, (H, W, C, N, Cd + K) (cbpdn.py:1565-1574)
         for name, v0, v1 in (('Y0', _lib.VAR_MY0, _lib.VAR_Y), ('U0', _lib.VAR_MU0, _lib.VAR_U)):
@@ -988,8 +988,17 @@ class ConvBPDNMaskDcpl(ConvBPDN):
     def _upload_weights(self):
         super(ConvBPDNMaskDcpl, self)._upload_weights()
         if hasattr(self, 'W'):
-            H, Wd = self.cri.Nv
-            self._dev.set_data_mask(_broadcastable(self.W, (H, Wd, self.cri.C, self.cri.K, 1)))
+            self._upload_mask()
+
+    def _upload_mask(self):
+        """The mask into the handle (a class whose block 0 is not the handle's own overrides this and
+        :meth:`_init_blocks`)."""
+        H, Wd = self.cri.Nv
+        self._dev.set_data_mask(_broadcastable(self.W, (H, Wd, self.cri.C, self.cri.K, 1)))
+
+    def _init_blocks(self):
+        """The two-block state at zero, the real signal beside it."""
+        self._dev.mdcpl_init(self.S)
 
     @property
     def _y0swap(self):

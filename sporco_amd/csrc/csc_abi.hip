@@ -690,6 +690,34 @@ int sporco_amd_csc_pd_setup(sporco_amd_csc_t h, const double *B, const double *Q
     SA_API_END
 }
 
+int sporco_amd_csc_pdl1_setup(sporco_amd_csc_t h, const double *B, const double *Q, const double *gamma,
+                              const void *S, int32_t cs, const void *mask) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(B && Q && gamma && S, "null argument");
+    h->impl->pdl1_setup(B, Q, gamma, S, cs, mask);
+    SA_API_END
+}
+
+int sporco_amd_csc_pdl1_block0(sporco_amd_csc_t h, int32_t which, int32_t upload, void *buf) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(buf, "null argument");
+    h->impl->pdl1_block0(which, upload != 0, buf);
+    SA_API_END
+}
+
+int sporco_amd_csc_pdl1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->pdl1_iter(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
 int sporco_amd_csc_pd_xstep(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
                             double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN

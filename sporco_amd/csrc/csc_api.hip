@@ -29,7 +29,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "inhib_update",     "tv_ystep",         "tv_adjoint",
                                     "rtv_solve",        "rtv_ystep",        "rtv_dual",
                                     "pd_solve",         "pd_recon",
-                                    "l1l1_y0step",      "l1l1_dual"};
+                                    "l1l1_y0step",      "l1l1_dual",
+                                    "pdl1_solve",       "pdl1_dual"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -37,7 +38,7 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
 // early-stop tests) and sporco_amd_csc_admm_run reads at its entry.
 struct Switches {
     bool unfused, old_rows, no_pad, no_vform, no_speculation, no_cols_sm, md_generic, cns_generic, cg_host,
-        placement_off, placement_force;
+        pdl1_generic, placement_off, placement_force;
     int persist;              // SPORCO_AMD_PERSIST: -1 unset (the hint decides), 0, 1
     int cols_sm_force_slab;   // SPORCO_AMD_COLS_SM_FORCE_SLAB: 0 unset
     static bool set(const char *name) { return std::getenv(name) != nullptr; }
@@ -52,6 +53,7 @@ struct Switches {
         s.md_generic = set("SPORCO_AMD_MD_GENERIC");
         s.cns_generic = set("SPORCO_AMD_CNS_GENERIC");
         s.cg_host = set("SPORCO_AMD_CG_HOST");
+        s.pdl1_generic = set("SPORCO_AMD_PDL1_GENERIC");
         const char *e = std::getenv("SPORCO_AMD_PLACEMENT");
         s.placement_off = e && e[0] == '0';
         s.placement_force = e && e[0] == 'f';      // "force": also for small arrays (tests)
@@ -437,6 +439,7 @@ template <typename T> struct Csc : CscBase {
         rtv_release();
         pd_release();
         l1l1_release();
+        pdl1_release();
         big_free(gemit);
         if (part_vpost) (void)hipFree(part_vpost);
         big_free(cols_out[0]);
@@ -615,6 +618,8 @@ template <typename T> struct Csc : CscBase {
         if (what == SPORCO_AMD_QUERY_CCMOD_GROUPS) return ccmod_group_count();
         if (what == SPORCO_AMD_QUERY_PD_WAVE_LAUNCHES) return pd_wave_launches;
         if (what == SPORCO_AMD_QUERY_PD_GENERIC_LAUNCHES) return pd_generic_launches;
+        if (what == SPORCO_AMD_QUERY_PDL1_WAVE_LAUNCHES) return pl_wave_launches;
+        if (what == SPORCO_AMD_QUERY_PDL1_GENERIC_LAUNCHES) return pl_generic_launches;
         if (what == SPORCO_AMD_QUERY_COLS_SM_FORM) return cols_sm_form.threads ? cols_sm_form.packed() : -1;
         throw Error(SPORCO_AMD_EINVAL, "unknown query");
     }
@@ -634,6 +639,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_rtv.inc"
 #include "api_pd.inc"
 #include "api_l1l1.inc"
+#include "api_pdl1.inc"
 };
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

@@ -19,6 +19,7 @@
 #include "csc_kernels.h"
 #include "csc_l1l1.h"
 #include "csc_pd.h"
+#include "csc_pdl1.h"
 #include "csc_pgm.h"
 #include "csc_rows.h"
 #include "csc_rtv.h"
@@ -99,6 +100,8 @@ enum ProfSlot {
     PS_PD_RECON,                // ... the reconstruction spectrum through B (reconstruct, fidelity at Y)
     PS_L1L1_Y0STEP,             // ConvL1L1Grd: relax + soft threshold + u step of block 0 (csc_l1l1.h)
     PS_L1L1_DUAL,               // ... both dual-residual norms in one read pass
+    PS_PDL1_SOLVE,              // ConvProdDictL1L1Grd: the eigen-channel diagonal-plus-rank-one x step (csc_pdl1.h)
+    PS_PDL1_DUAL,               // ... the norm of A^T u through B in one read pass
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -243,6 +246,10 @@ struct CscBase {
     virtual void pd_xstep(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void pd_dfid(int var, double *out_dev) = 0;
     virtual void pd_reconstruct(int var, void *dst) = 0;
+    virtual void pdl1_setup(const double *B, const double *Q, const double *gamma, const void *S, int cs,
+                            const void *mask) = 0;
+    virtual void pdl1_block0(int which, bool to_device, void *host) = 0;
+    virtual void pdl1_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void read_out(const double *out_dev, double *out_host) = 0;
     double *out_dev_default = nullptr;
     Profiler prof;

@@ -46,6 +46,16 @@ template <typename T> __device__ __forceinline__ cx<T> wave_sum_cx(cx<T> v) {
     return v;
 }
 
+// V consecutive complex values in one load (16 bytes for V = 2 in float32 and V = 1 in float64)
+template <typename T, int V> struct alignas(V * sizeof(cx<T>)) CxVec {
+    cx<T> v[V];
+};
+
+// the value of lane `src`: an xor shuffle whose mask differs from lane to lane (lane ^ mask = src)
+template <typename T> __device__ __forceinline__ cx<T> wave_pick(cx<T> v, int lane, int src) {
+    return mk<T>(__shfl_xor(v.re, lane ^ src, kWave), __shfl_xor(v.im, lane ^ src, kWave));
+}
+
 // Weighted gradient spectrum w_k * sum_i |G_i|^2 at (pixel, filter): GHGf of cbpdn.py:1141-1143
 template <typename T>
 __device__ __forceinline__ T grad_gh(const GradTerm<T> &g, int64_t pix, int Wf) {

@@ -36,17 +36,8 @@ __global__ void __launch_bounds__(kThreads) l1l1_y0step_kernel(const L1Y0Args<T>
     block_sum_store<5>(acc, dyn_lds<double>(), partials + (int64_t)blockIdx.x * 5);
 }
 
-// V consecutive filters of one (pixel, image) system per thread, one load of V cx<T> each (16 bytes
-// for V = 2 in float32 and V = 1 in float64); G = K / V threads a system.
-template <typename T, int V> struct alignas(V * sizeof(cx<T>)) CxVec {
-    cx<T> v[V];
-};
-
-// the value of lane `src`: an xor shuffle whose mask differs from lane to lane (lane ^ mask = src)
-template <typename T> __device__ __forceinline__ cx<T> wave_pick(cx<T> v, int lane, int src) {
-    return mk<T>(__shfl_xor(v.re, lane ^ src, kWave), __shfl_xor(v.im, lane ^ src, kWave));
-}
-
+// V consecutive filters of one (pixel, image) system per thread, one load of V cx<T> each (CxVec: 16
+// bytes for V = 2 in float32 and V = 1 in float64); G = K / V threads a system.
 // The block-0 values of a system (Cd of dy0f, Cd of u0f) are the same for its G threads.  A wave's
 // 64 threads lie in at most 64 consecutive systems: lane j loads the values of the wave's j-th system
 // once, and every thread picks those of its own system from that lane.  The loop runs to a multiple
