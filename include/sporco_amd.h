@@ -695,6 +695,22 @@ int sporco_amd_csc_mdcpl_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *
 int sporco_amd_csc_l1l1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
                              double out[SPORCO_AMD_OUT_COUNT]);
 
+/* ---- l1 objective inside l2 balls: sporco.admm.cbpdn.ConvMinL1InL2Ball (cbpdn.py:1830-2060),
+ * minimise sum_m ||x_m||_1 such that ||sum_m d_m * x_m - s_k||_2 <= epsilon for every channel and image
+ * k, on the state of the mask-decoupling calls above (sporco_amd_csc_mdcpl_init; L1Weight through
+ * set_l1_weight; the data mask is not read).
+ * One iteration.  params as for mdcpl_iter; EPSILON TRAVELS IN params.mu, which mdcpl_iter leaves unused
+ * (SPORCO_AMD_FLAG_GRADREG is refused, as there); lmbda = 1 gives block 1 the reference's threshold
+ * wl1 / rho.  xstep, relax_AX, block 1 and ustep as mdcpl_iter, on the same two paths (the
+ * register-resident kernels where mdcpl_iter takes them, else the generic chain; SPORCO_AMD_MD_GENERIC
+ * forces the latter); ystep of block 0 (:2024-2026): y0 = proj_l2(AX0 + u0 - s, epsilon), one ball per
+ * channel and image with the norm over the image plane (csrc/csc_ball.h).  out as for mdcpl_iter, except:
+ * DFID, which this class has no other use for, holds the constraint measure sum_p max(g_p - epsilon, 0)^2
+ * over the planes p, g_p the plane norm of AXnr0 - s, or of the new y0 with GEVAL_Y -- the square of the
+ * reference's ||proj_l2(g0) - g0|| (:2034-2040). */
+int sporco_amd_csc_ball_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]);
+
 /* ---- ADMM with inhibition: sporco.admm.cbpdnin.ConvBPDNInhib (cbpdnin.py:28-352) -------------
  * The iteration is the ConvBPDN one (sporco_amd_csc_admm_iter, or the staged calls) with an array
  * l1 weight that sporco_amd_csc_inhib_update rewrites after every iteration: the thresholds
@@ -1007,6 +1023,10 @@ int sporco_amd_prox_l1w(int dtype, const int64_t shape[5], const void *v, const 
  * of real v shaped (outer, C, inner). */
 int sporco_amd_prox_sl1l2(int dtype, int64_t outer, int32_t C, int64_t inner, const void *v,
                           double alpha, double beta, void *out);
+/* proj_l2 (sporco/prox/_lp.py:334-340): projection onto the l2 ball of radius gamma, the norm over the
+ * middle axis of real v shaped (outer, C, inner); a vector of norm 0 stays 0. */
+int sporco_amd_proj_l2(int dtype, int64_t outer, int64_t C, int64_t inner, const void *v, double gamma,
+                       void *out);
 /* rfl2norm2 (sporco/fft.py:449-484) of complex xf (H,W/2+1,P) for spatial (H,W). */
 int sporco_amd_rfl2norm2(int dtype, int32_t H, int32_t W, int64_t P, const void *xf,
                          double *out);

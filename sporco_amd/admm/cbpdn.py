@@ -1263,6 +1263,111 @@ class ConvL1L1Grd(ConvBPDNMaskDcpl):
         multi-channel solve are rebuilt on the device when it moves)."""
 
 
+class ConvMinL1InL2Ball(ConvBPDNMaskDcpl):
+    r"""Convolutional sparse coding with an l1 objective inside l2 balls: minimise
+    sum_m ||x_m||_1 such that ||sum_m d_m * x_m - s_k||_2 <= epsilon for every channel and image k,
+    through the two-block constraint of :class:`ConvBPDNMaskDcpl` (reference class:
+    sporco/admm/cbpdn.py:1830-2060) -- the constrained counterpart of :class:`ConvBPDN`, for a known
+    noise level instead of a ``lmbda``.
+
+    One iteration is one call of ``sporco_amd_csc_ball_iter``: the x step, block 1 (a soft threshold
+    by ``L1Weight / rho``), the dual update and the dual residual are those of the parent class, on
+    the register-resident kernels where the parent takes them (float32, H and W in 128 / 256 / 512 or
+    a mixed-radix length, even K <= 64, single-channel dictionary) and on the generic chain otherwise;
+    block 0 is projected onto the l2 balls by two kernels of its own (csrc/csc_ball.h).
+
+    In scope: ``dimN = 2``, float32 / float64, ``dimK`` 0 / 1, multi-channel signals and dictionaries
+    (at most 8 dictionary channels), scalar or array ``L1Weight``, ``NonNegCoef``, ``NoBndryCross``,
+    ``AutoRho`` (on by default, as in the reference), ``RelaxParam``, ``AuxVarObj``, ``LinSolveCheck``,
+    ``Y0`` / ``U0`` (concatenated blocks), ``ReturnVar``, ``setdict``.  ``HighMemSolve`` is accepted and
+    has no effect.  A ``Y0`` without ``U0`` starts the dual variable by the reference's rule
+    (:2003-2015), which the reference itself can evaluate for a single image only.  Refused with
+    ``NotImplementedError``: ``dimN`` 1 / 3, complex data, ``reducer=``, resident or device-array
+    inputs, pickling.
+
+    IterationStats fields: ``Iter, ObjFun, Cnstr, PrimalRsdl, DualRsdl, EpsPrimal, EpsDual, Rho,
+    XSlvRelRes, Time``.  ``ObjFun`` is ||wl1 g1||_1 with g1 = X, or Y1 under ``AuxVarObj``; ``Cnstr``
+    is ||proj_l2(g0) - g0|| with g0 = D x - s, or Y0 under ``AuxVarObj``.
+    """
+
+    class Options(ConvBPDNMaskDcpl.Options):
+        """The reference's defaults (cbpdn.py:1927-1934): those of :class:`ConvBPDNMaskDcpl` with
+        ``AutoRho`` enabled (``Period`` 10, ``AutoScaling``, ``Scaling`` 1000, ``RsdlRatio`` 1.2,
+        ``RsdlTarget`` 1)."""
+
+        defaults = copy.deepcopy(ConvBPDNMaskDcpl.Options.defaults)
+        defaults['AutoRho'].update({'Enabled': True, 'Period': 10, 'AutoScaling': True,
+                                    'Scaling': 1000.0, 'RsdlRatio': 1.2, 'RsdlTarget': 1.0})
+
+        def __init__(self, opt=None):
+            ConvBPDNMaskDcpl.Options.__init__(self, {} if opt is None else opt)
+
+    itstat_fields_objfn = ('ObjFun', 'Cnstr')
+    hdrtxt_objfn = ('Fnc', 'Cnstr')
+    hdrval_objfun = {'Fnc': 'ObjFun', 'Cnstr': 'Cnstr'}
+
+    def __init__(self, D, S, epsilon, opt=None, dimK=None, dimN=2, **backend):
+        name = type(self).__name__
+        if opt is None:
+            opt = ConvMinL1InL2Ball.Options()
+        if dimN != 2:
+            raise NotImplementedError("%s: dimN = 2 (images)" % name)
+        if backend.get('reducer') is not None:
+            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
+        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, S)):
+            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
+        if np.iscomplexobj(D) or np.iscomplexobj(S):
+            raise NotImplementedError("%s handles real-valued D and S" % name)
+        self.set_dtype(opt, S.dtype)
+        self.epsilon = self.dtype.type(epsilon)
+        if not self.epsilon >= 0:
+            raise ValueError("epsilon must not be negative")
+        super(ConvMinL1InL2Ball, self).__init__(D, S, 1.0, None, opt, dimK=dimK, dimN=dimN, **backend)
+        if self.opt['Y0'] is not None and self.opt['U0'] is None:
+            self._dual_from_y0(np.asarray(self.opt['Y0']), np.shape(S))
+
+    def _dual_from_y0(self, Y0, shape_S):
+        """The reference's ``uinit`` (cbpdn.py:2003-2015): U0 = sign(block 0 of Y) / rho, U1 = block 1
+        of Y - S, with the signal as it was handed in, trailing unit axes appended.  That difference
+        has the shape of block 1 only when the image index has extent one and block 0 is not swapped
+        onto the filter axis; the reference fails on every other problem, and so does this."""
+        cri = self.cri
+        shp_s = tuple(shape_S) + (1,) * (cri.dimN + 3 - len(shape_S))
+        shp_1 = cri.shpX
+        try:
+            ok = np.broadcast_shapes(shp_s, shp_1) == tuple(shp_1) and not self._y0swap
+        except ValueError:
+            ok = False
+        if not ok:
+            raise ValueError("Y0 without U0: the reference's initial dual variable subtracts the signal "
+                             "viewed as %s from block 1 of Y0, of shape %s, and joins the result to a "
+                             "block 0 of shape %s; these shapes do not fit (a single image is needed)"
+                             % (shp_s, tuple(shp_1), tuple(cri.shpS)))
+        Y0 = np.asarray(Y0, dtype=self.dtype).reshape(cri.shpX[:-1] + (cri.Cd + cri.M,))
+        U0 = np.sign(self.block_sep0(Y0)) / self.rho
+        U1 = self.block_sep1(Y0) - self.S.reshape(shp_s)
+        self._set_blocks(self.block_cat(U0, U1), _lib.VAR_MU0, _lib.VAR_U)
+
+    def _upload_mask(self):
+        """No data mask: block 0 is a projection, not a weighted division."""
+
+    def _mu_eff(self):
+        # (epsilon travels in the parameter struct's mu, which the mask-decoupling iteration leaves unused)
+        return float(self.epsilon)
+
+    def __getstate__(self):
+        raise NotImplementedError("%s: pickling is not offered" % type(self).__name__)
+
+    def _device_iteration(self, p):
+        return self._dev.ball_iter(p)
+
+    def eval_objfn(self):
+        """||wl1 g1||_1 and the constraint measure ||proj_l2(g0) - g0|| (cbpdn.py:2034-2060)."""
+        g1v = abs(self._wl1_scalar) * self._sums[_lib.OUT_L1]
+        g0v = float(np.sqrt(self._sums[_lib.OUT_DFID]))
+        return (g1v, g0v)
+
+
 class AddMaskSim(object):
     """Boundary / missing-data masking by additive mask simulation: wrapper about a
     ConvBPDN-family object of this module with an impulse filter appended to the

@@ -29,11 +29,74 @@
     //                                rfftn(u1)|^2 in registers (one read pass, nothing written)
     // against the generic chain's four 2-D FFTs of X-sized arrays plus their glue passes.
     cx<T> *md_sft = nullptr, *md_coef = nullptr;
+    // Block 0 given AXnr = D x in sreal: relax, y0, u0 and the five sums of the block.  y0 is the
+    // mask-decoupling division (md_y0step) or -- ball, ConvMinL1InL2Ball -- the projection of
+    // AX0 + U0 - S onto the l2 ball of radius p.mu, one ball per channel and image with the norm
+    // over the image plane (csc_ball.h: two passes and the totals between them).  The ball class
+    // has no data mask and leaves OUT_DFID to the constraint measure.
+    double *ball_ws = nullptr;
+    int64_t ball_ws_n = 0;
+    void md_block0(const sporco_amd_admm_params &p, double *out_dev, bool ball) {
+        T *Y0 = rv(SPORCO_AMD_VAR_MY0), *U0 = rv(SPORCO_AMD_VAR_MU0);
+        const T us = (T)p.u_scale;
+        int nb;
+        if (ball) {
+            const BallGeom g = ball_geom(sizeof(T), 1, (int64_t)H * W, CNs);
+            if (ball_ws_n < g.workspace_doubles()) {
+                if (ball_ws) SA_HIP(hipFree(ball_ws));
+                ball_ws = nullptr;
+                ball_ws_n = 0;
+                SA_HIP(hipMalloc((void **)&ball_ws, sizeof(double) * g.workspace_doubles()));
+                ball_ws_n = g.workspace_doubles();
+            }
+            BallArgs<T> ba;
+            ba.ax0nr = sreal;
+            ba.y0 = Y0;
+            ba.u0 = U0;
+            ba.s = md_s;
+            ba.eps = p.mu;
+            ba.rlx = (T)p.rlx;
+            ba.us = us;
+            ba.geval_y = (p.flags & F_GEVAL_Y) ? 1 : 0;
+            ba.ws = ball_ws;
+            {
+                ProfScope ps(prof, PS_BALL_NORMS);
+                launch_ball_norms<T>(st, ba, g);
+                launch_ball_totals(st, ball_ws, g);
+            }
+            {
+                ProfScope ps(prof, PS_BALL_Y0STEP);
+                nb = launch_ball_y0step<T>(st, ba, g, part_a);
+            }
+        } else {
+            MdY0Args<T> ya;
+            ya.ax0nr = sreal;
+            ya.y0 = Y0;
+            ya.u0 = U0;
+            ya.s = md_s;
+            ya.w = have_wdat ? wdat : Weight<T>();
+            ya.rho = (T)p.rho;
+            ya.rlx = (T)p.rlx;
+            ya.us = us;
+            ya.geval_y = (p.flags & F_GEVAL_Y) ? 1 : 0;
+            ya.H = H;
+            ya.W = W;
+            ya.C = Cs;
+            ya.N = N;
+            ProfScope ps(prof, PS_OTHER);
+            nb = launch_md_y0step<T>(st, ya, part_a);
+        }
+        const int slots[5] = {SPORCO_AMD_OUT_L21, SPORCO_AMD_OUT_RGR, SPORCO_AMD_OUT_CNSTR,
+                              SPORCO_AMD_OUT_CGIT, SPORCO_AMD_OUT_DFID};
+        const double scales[5] = {1, 1, 1, 1, 1};
+        finalize(part_a, nb, 5, 5, slots, scales, out_dev);
+    }
+
     bool mdcpl_fused_ok(const sporco_amd_admm_params &p) const {
         return std::is_same<T, float>::value && rows_ok && mr_ok(p) && fused && !tail_mode && !fused_mc && Cd == 1 &&
                !(p.flags & F_XRRS) && p.lmbda >= 0.0 && !sw.md_generic;
     }
-    void mdcpl_iter_fused(const sporco_amd_admm_params &p, double *out_dev) {
+    void mdcpl_iter_fused(const sporco_amd_admm_params &p, double *out_dev, bool ball) {
         const int64_t ns = (int64_t)H * W * CNs, nsf = npix * CN;
         const T us = (T)p.u_scale;
         T *Y1 = rv(SPORCO_AMD_VAR_Y), *U1 = rv(SPORCO_AMD_VAR_U), *X = rv(SPORCO_AMD_VAR_X);
@@ -101,30 +164,7 @@
             const double scales[6] = {1, 0, 1, 1, 1, 1};
             finalize(part_rows, (int)nt, 8, 6, slots, scales, out_dev);
         }
-        MdY0Args<T> ya;
-        ya.ax0nr = sreal;
-        ya.y0 = Y0;
-        ya.u0 = U0;
-        ya.s = md_s;
-        ya.w = have_wdat ? wdat : Weight<T>();
-        ya.rho = (T)p.rho;
-        ya.rlx = (T)p.rlx;
-        ya.us = us;
-        ya.geval_y = (p.flags & F_GEVAL_Y) ? 1 : 0;
-        ya.H = H;
-        ya.W = W;
-        ya.C = Cs;
-        ya.N = N;
-        {
-            ProfScope ps(prof, PS_OTHER);
-            nb = launch_md_y0step<T>(st, ya, part_a);
-        }
-        {
-            const int slots[5] = {SPORCO_AMD_OUT_L21, SPORCO_AMD_OUT_RGR, SPORCO_AMD_OUT_CNSTR,
-                                  SPORCO_AMD_OUT_CGIT, SPORCO_AMD_OUT_DFID};
-            const double scales[5] = {1, 1, 1, 1, 1};
-            finalize(part_a, nb, 5, 5, slots, scales, out_dev);
-        }
+        md_block0(p, out_dev, ball);
         if (p.flags & F_RESID) {
             fwd2(U0, nullptr, T(0), innerb, CNs);
             {
@@ -144,7 +184,14 @@
         }
     }
 
-    void mdcpl_iter(const sporco_amd_admm_params &p, double *out_dev) override {
+    void mdcpl_iter(const sporco_amd_admm_params &p, double *out_dev) override { md_iterate(p, out_dev, false); }
+    // ConvMinL1InL2Ball (sporco/admm/cbpdn.py:1830-2060): the same iteration with block 0 projected
+    // onto the l2 balls of radius p.mu (md_block0); the handle's data mask is not read
+    void ball_iter(const sporco_amd_admm_params &p, double *out_dev) override {
+        SA_REQUIRE(p.mu >= 0.0, "epsilon (params.mu) must not be negative");
+        md_iterate(p, out_dev, true);
+    }
+    void md_iterate(const sporco_amd_admm_params &p, double *out_dev, bool ball) {
         require_ready();
         SA_REQUIRE(md_s != nullptr, "mdcpl_init must be called first");
         SA_REQUIRE(p.rho > 0.0, "rho must be positive");
@@ -153,7 +200,7 @@
         if (mdcpl_fused_ok(p)) md_x_pending = false;   // (X of the previous iteration is superseded)
         before_state_change();
         if (mdcpl_fused_ok(p)) {
-            mdcpl_iter_fused(p, out_dev);
+            mdcpl_iter_fused(p, out_dev, ball);
             return;
         }
         x_written();
@@ -236,30 +283,7 @@
             const double scales[6] = {1, 0, 1, 1, 1, 1};
             finalize(part_b, nb, 8, 6, slots, scales, out_dev);
         }
-        MdY0Args<T> ya;
-        ya.ax0nr = sreal;
-        ya.y0 = Y0;
-        ya.u0 = U0;
-        ya.s = md_s;
-        ya.w = have_wdat ? wdat : Weight<T>();
-        ya.rho = (T)p.rho;
-        ya.rlx = (T)p.rlx;
-        ya.us = us;
-        ya.geval_y = (p.flags & F_GEVAL_Y) ? 1 : 0;
-        ya.H = H;
-        ya.W = W;
-        ya.C = Cs;
-        ya.N = N;
-        {
-            ProfScope ps(prof, PS_OTHER);
-            nb = launch_md_y0step<T>(st, ya, part_a);
-        }
-        {
-            const int slots[5] = {SPORCO_AMD_OUT_L21, SPORCO_AMD_OUT_RGR, SPORCO_AMD_OUT_CNSTR,
-                                  SPORCO_AMD_OUT_CGIT, SPORCO_AMD_OUT_DFID};
-            const double scales[5] = {1, 1, 1, 1, 1};
-            finalize(part_a, nb, 5, 5, slots, scales, out_dev);
-        }
+        md_block0(p, out_dev, ball);
         if (p.flags & F_RESID) {
             // dual residual (cbpdn.py:1814-1818): A^T u = irfftn(conj(Df) rfftn(u0)) + u1, its
             // norm through the half-spectrum Parseval sum

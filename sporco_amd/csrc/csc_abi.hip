@@ -579,6 +579,17 @@ int sporco_amd_csc_l1l1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p
     SA_API_END
 }
 
+int sporco_amd_csc_ball_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
+                             double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE(h);
+    SA_REQUIRE(p && out, "null argument");
+    double *dev = stats_buf(h);
+    h->impl->ball_iter(*p, dev);
+    h->impl->read_out(dev, out);
+    SA_API_END
+}
+
 int sporco_amd_csc_inhib_setup(sporco_amd_csc_t h, const double *Wg, int32_t Ng,
                                const double *taps_rows, int32_t ntaps_rows, const double *taps_cols,
                                int32_t ntaps_cols, int32_t want_self, double lmbda) {

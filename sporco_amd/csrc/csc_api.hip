@@ -30,6 +30,7 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "rtv_solve",        "rtv_ystep",        "rtv_dual",
                                     "pd_solve",         "pd_recon",
                                     "l1l1_y0step",      "l1l1_dual",
+                                    "ball_norms",       "ball_y0step",
                                     "pdl1_solve",       "pdl1_dual"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
@@ -454,7 +455,7 @@ template <typename T> struct Csc : CscBase {
         work = nullptr;
         for (void *p : {(void *)pst_part_rows, (void *)pst_part_f, pst_blk, (void *)pst_ctl, (void *)pst_bar,
                         (void *)cns_w, (void *)cns_sft, (void *)flt_h, (void *)flt_w,
-                        (void *)zf_ch, (void *)zfv_buf, (void *)md_sft, (void *)md_coef, (void *)pgm_rx[0], (void *)pgm_rx[1]})
+                        (void *)zf_ch, (void *)zfv_buf, (void *)md_sft, (void *)md_coef, (void *)ball_ws, (void *)pgm_rx[0], (void *)pgm_rx[1]})
             if (p) (void)hipFree(p);
         for (void *p : {(void *)dft, (void *)sft, (void *)gramt, (void *)part_f, (void *)twA, (void *)twB,
                         (void *)twRows, (void *)part_rows, (void *)y_alt, (void *)u_alt, (void *)part_pgm, (void *)part_pgm2, (void *)ccmod_r, (void *)pgm_ey, (void *)gpart,

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "csc_ball.h"
 #include "csc_fused.h"
 #include "csc_inhib.h"
 #include "csc_kernels.h"
@@ -100,6 +101,8 @@ enum ProfSlot {
     PS_PD_RECON,                // ... the reconstruction spectrum through B (reconstruct, fidelity at Y)
     PS_L1L1_Y0STEP,             // ConvL1L1Grd: relax + soft threshold + u step of block 0 (csc_l1l1.h)
     PS_L1L1_DUAL,               // ... both dual-residual norms in one read pass
+    PS_BALL_NORMS,              // ConvMinL1InL2Ball: the plane norms of block 0, tiles and totals (csc_ball.h)
+    PS_BALL_Y0STEP,             // ... relax + projection onto the l2 balls + u step of block 0
     PS_PDL1_SOLVE,              // ConvProdDictL1L1Grd: the eigen-channel diagonal-plus-rank-one x step (csc_pdl1.h)
     PS_PDL1_DUAL,               // ... the norm of A^T u through B in one read pass
     PS_COUNT
@@ -227,6 +230,7 @@ struct CscBase {
     virtual void mdcpl_init(const void *S) = 0;
     virtual void mdcpl_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void l1l1_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void ball_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void dstep_init(const void *Y0) = 0;
     virtual void dstep_md_init(const void *Y0, const void *S) = 0;
     virtual void dstep_iter(const sporco_amd_dstep_params &p, double *out_dev) = 0;

@@ -207,6 +207,26 @@ void prim_prox_sl1l2(int64_t outer, int C, int64_t inner, const void *v, double 
     SA_HIP(hipMemcpy(out, dout.p, sizeof(T) * n, hipMemcpyDeviceToHost));
 }
 
+// proj_l2: the two passes of csc_ball.h on a plain array (no relaxation, no dual variable)
+template <typename T>
+void prim_proj_l2(int64_t outer, int64_t C, int64_t inner, const void *v, double gamma, void *out) {
+    const int64_t n = outer * C * inner;
+    const BallGeom g = ball_geom(sizeof(T), outer, C, inner);
+    DevBuf dv(sizeof(T) * n), dout(sizeof(T) * n), dws(sizeof(double) * g.workspace_doubles()),
+        dpart(sizeof(double) * kMaxPartialBlocks * 5);
+    SA_HIP(hipMemcpy(dv.p, v, sizeof(T) * n, hipMemcpyHostToDevice));
+    BallArgs<T> a;
+    a.ax0nr = dv.as<T>();
+    a.y0 = dout.as<T>();
+    a.eps = gamma;
+    a.ws = dws.as<double>();
+    launch_ball_norms<T>(nullptr, a, g);
+    launch_ball_totals(nullptr, a.ws, g);
+    launch_ball_y0step<T>(nullptr, a, g, dpart.as<double>());
+    SA_HIP(hipDeviceSynchronize());
+    SA_HIP(hipMemcpy(out, dout.p, sizeof(T) * n, hipMemcpyDeviceToHost));
+}
+
 template <typename T> void prim_rfl2norm2(int H, int W, int64_t P, const void *xf, double *out) {
     const int64_t npix = (int64_t)H * (W / 2 + 1);
     DevBuf dx(sizeof(cx<T>) * npix * P), dpart(sizeof(double) * kMaxPartialBlocks),
@@ -357,6 +377,14 @@ int sporco_amd_prox_sl1l2(int dtype, int64_t outer, int32_t C, int64_t inner, co
     SA_API_BEGIN
     SA_REQUIRE(v && out && outer >= 1 && C >= 1 && inner >= 1, "bad argument");
     SA_DISPATCH(dtype, prim_prox_sl1l2, outer, C, inner, v, alpha, beta, out)
+    SA_API_END
+}
+
+int sporco_amd_proj_l2(int dtype, int64_t outer, int64_t C, int64_t inner, const void *v, double gamma,
+                       void *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(v && out && outer >= 1 && C >= 1 && inner >= 1 && gamma >= 0.0, "bad argument");
+    SA_DISPATCH(dtype, prim_proj_l2, outer, C, inner, v, gamma, out)
     SA_API_END
 }
 

@@ -1,9 +1,9 @@
 """Device proximal operators with the signatures of ``sporco.prox``.
 
-``prox_l1`` (sporco/prox/_lp.py:144-183) and ``prox_sl1l2``
-(sporco/prox/_l21.py:51-88) for real arrays and scalar parameters; inside the
-solvers the same arithmetic runs fused into the ADMM / PGM epilogue kernels,
-where weight arrays are supported.
+``prox_l1`` (sporco/prox/_lp.py:144-183), ``prox_sl1l2``
+(sporco/prox/_l21.py:51-88) and ``proj_l2`` (sporco/prox/_lp.py:334-340) for
+real arrays and scalar parameters; inside the solvers the same arithmetic runs
+fused into the ADMM / PGM epilogue kernels, where weight arrays are supported.
 """
 
 import numpy as np
@@ -73,6 +73,35 @@ def prox_sl1l2(v, alpha, beta, axis=None):
 def prox_l2(v, alpha, axis=None):
     """v/||v|| * max(0, ||v|| - alpha): the alpha_1 = 0 case of :func:`prox_sl1l2`."""
     return prox_sl1l2(v, 0.0, alpha, axis)
+
+
+def proj_l2(v, gamma, axis=None):
+    """Projection onto the l2 ball of radius ``gamma``, the norm taken over ``axis``: None (the whole
+    array), an int, or a tuple of adjacent axes (sporco/prox/_lp.py:334-340).  A vector of norm 0 is
+    returned as it is."""
+    if np.ndim(gamma) != 0:
+        raise NotImplementedError("array-valued parameters are handled inside the solvers only")
+    v = _real(v)
+    if axis is None:
+        outer, C, inner = 1, v.size, 1
+    else:
+        if isinstance(axis, (int, np.integer)):
+            axes = (int(axis) % v.ndim,)
+        elif isinstance(axis, (tuple, list)) and len(axis) > 0 and \
+                all(isinstance(a, (int, np.integer)) for a in axis):
+            axes = tuple(sorted(int(a) % v.ndim for a in axis))
+        else:
+            raise NotImplementedError("axis must be None, an int or a tuple of adjacent axes")
+        if axes != tuple(range(axes[0], axes[0] + len(axes))):
+            raise NotImplementedError("the l2 axes must be adjacent: %s" % (axis,))
+        outer = int(np.prod(v.shape[:axes[0]], dtype=np.int64))
+        C = int(np.prod(v.shape[axes[0]:axes[-1] + 1], dtype=np.int64))
+        inner = int(np.prod(v.shape[axes[-1] + 1:], dtype=np.int64))
+    out = np.empty_like(v)
+    if v.size:
+        _lib.check(_lib.lib().sporco_amd_proj_l2(_lib.dtype_code(v.dtype), outer, C, inner, _lib._ptr(v),
+                                                 float(gamma), _lib._ptr(out)))
+    return out
 
 
 def norm_l1(x, axis=None):
