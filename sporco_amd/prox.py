@@ -22,7 +22,11 @@ def _real(v):
 
 def prox_l1(v, alpha):
     """sign(v) * max(|v| - alpha, 0); ``alpha`` a scalar or an array that broadcasts against
-    ``v`` (sporco/prox/_lp.py:144-183)."""
+    ``v`` (sporco/prox/_lp.py:144-183).
+
+    The kernel works in the precision of ``v`` and the result has ``v``'s dtype: ``alpha`` is rounded to
+    that dtype first.  A float32 ``v`` with a float64 ``alpha`` array therefore gives the float32 result
+    of the float32 weights, where NumPy's promotion would have returned float64."""
     v = _real(v)
     out = np.empty_like(v)
     if np.ndim(alpha) == 0:
@@ -48,7 +52,11 @@ def prox_l1(v, alpha):
 
 
 def prox_sl1l2(v, alpha, beta, axis=None):
-    """prox of alpha*||.||_1 + beta*||.||_2 with the l2 norm over ``axis``."""
+    """prox of alpha*||.||_1 + beta*||.||_2 with the l2 norm over ``axis``.
+
+    One thread forms the sum of squares of a group, member by member, in the precision of ``v``; with
+    ``axis=None`` the whole array is one group.  For float32 that is the accuracy of a sequential
+    float32 sum (relative error 7e-8 on 4096 standard normal values), not that of a float64 one."""
     if np.ndim(alpha) != 0 or np.ndim(beta) != 0:
         raise NotImplementedError("array-valued parameters are handled inside the solvers only")
     v = _real(v)
