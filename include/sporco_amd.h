@@ -711,6 +711,25 @@ int sporco_amd_csc_l1l1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p
 int sporco_amd_csc_ball_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p,
                              double out[SPORCO_AMD_OUT_COUNT]);
 
+/* ---- ConvBPDN inside l1 balls: sporco.admm.cbpdn.ConvBPDNProjL1 (cbpdn.py:1220-1395),
+ * minimise (1/2) ||sum_m d_m * x_m - s||^2 such that sum_m ||x_m||_1 <= gamma for every image, on the
+ * state of sporco_amd_csc_admm_iter (VAR_X, VAR_Y, VAR_U).
+ * One iteration: the x step of admm_iter with lmbda = 0 (the same launches as sporco_amd_csc_admm_xstep),
+ * the threshold search of the projection of AX + U onto one l1 ball per image (csrc/csc_projl1.h: a few
+ * streaming reduction passes, no sort), and one pass that relaxes, shrinks by the image's threshold,
+ * applies NonNegCoef / NoBndryCross and updates the dual variable.  params as for admm_iter (lmbda and mu
+ * are not read).  out as for admm_iter, except:
+ *   OUT_L1, which this class has no other use for, holds the squared constraint measure
+ *     sum_n sum_i min(|g_i|, tau_n(g))^2 = ||proj_l1(g) - g||^2, g = X, or the new Y with GEVAL_Y
+ *     (:1385-1395); it takes a threshold search of its own and is formed with FLAG_OBJ only;
+ *   OUT_CGIT is the number of images whose search had not ended when the call returned (always 0: the
+ *     call enqueues further passes until every search has ended and never applies another threshold);
+ *   OUT_CNSTR is the same count for the constraint measure's search (always 0 on return, likewise);
+ *   OUT_CGN / OUT_RGRX are the search passes the slowest image took (y step / constraint measure).
+ * SPORCO_AMD_EUNSUPPORTED: a volume handle, a handle with a communicator, complex data. */
+int sporco_amd_csc_projl1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p, double gamma,
+                               double out[SPORCO_AMD_OUT_COUNT]);
+
 /* ---- ADMM with inhibition: sporco.admm.cbpdnin.ConvBPDNInhib (cbpdnin.py:28-352) -------------
  * The iteration is the ConvBPDN one (sporco_amd_csc_admm_iter, or the staged calls) with an array
  * l1 weight that sporco_amd_csc_inhib_update rewrites after every iteration: the thresholds
@@ -1026,6 +1045,12 @@ int sporco_amd_prox_sl1l2(int dtype, int64_t outer, int32_t C, int64_t inner, co
 /* proj_l2 (sporco/prox/_lp.py:334-340): projection onto the l2 ball of radius gamma, the norm over the
  * middle axis of real v shaped (outer, C, inner); a vector of norm 0 stays 0. */
 int sporco_amd_proj_l2(int dtype, int64_t outer, int64_t C, int64_t inner, const void *v, double gamma,
+                       void *out);
+/* proj_l1 (sporco/prox/_l1proj.py:24-154): Euclidean projection onto the l1 ball of radius gamma of
+ * each of the P interleaved sets of real v shaped (outer, P, inner) -- element i belongs to set
+ * (i / inner) % P, and the norm of a set runs over its outer and inner indices; P = 1: the whole array.
+ * A set with l1 norm <= gamma comes back bit for bit. */
+int sporco_amd_proj_l1(int dtype, int64_t outer, int64_t P, int64_t inner, const void *v, double gamma,
                        void *out);
 /* rfl2norm2 (sporco/fft.py:449-484) of complex xf (H,W/2+1,P) for spatial (H,W). */
 int sporco_amd_rfl2norm2(int dtype, int32_t H, int32_t W, int64_t P, const void *xf,

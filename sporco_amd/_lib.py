@@ -85,7 +85,7 @@ EXPORTS = (
     'sporco_amd_csc_ccmod_getdict', 'sporco_amd_csc_setdict_from_dstep', 'sporco_amd_csc_asum',
     'sporco_amd_csc_set_filter_sizes', 'sporco_amd_csc_cns_init', 'sporco_amd_csc_cns_iter', 'sporco_amd_csc_cns_md_init', 'sporco_amd_csc_cns_mean_ptr',
     'sporco_amd_csc_dstep_init', 'sporco_amd_csc_dstep_iter', 'sporco_amd_csc_ccmod_sgd_step',
-    'sporco_amd_csc_mdcpl_init', 'sporco_amd_csc_mdcpl_iter', 'sporco_amd_csc_l1l1_iter', 'sporco_amd_csc_ball_iter', 'sporco_amd_csc_dstep_md_init',
+    'sporco_amd_csc_mdcpl_init', 'sporco_amd_csc_mdcpl_iter', 'sporco_amd_csc_l1l1_iter', 'sporco_amd_csc_ball_iter', 'sporco_amd_csc_projl1_iter', 'sporco_amd_csc_dstep_md_init',
     'sporco_amd_csc_set_data_mask', 'sporco_amd_csc_masked_grad',
     'sporco_amd_csc_inhib_setup', 'sporco_amd_csc_inhib_update',
     'sporco_amd_csc_tv_setup', 'sporco_amd_csc_tv_xstep', 'sporco_amd_csc_tv_ystep', 'sporco_amd_csc_tv_adjoint',
@@ -102,7 +102,7 @@ EXPORTS = (
     'sporco_amd_csc_set_comm',
     'sporco_amd_rfftn2', 'sporco_amd_irfftn2', 'sporco_amd_solvedbi_sm',
     'sporco_amd_inner', 'sporco_amd_prox_l1', 'sporco_amd_prox_l1w', 'sporco_amd_prox_sl1l2',
-    'sporco_amd_proj_l2', 'sporco_amd_rfl2norm2',
+    'sporco_amd_proj_l2', 'sporco_amd_proj_l1', 'sporco_amd_rfl2norm2',
 )
 
 
@@ -324,6 +324,7 @@ def load(path=None):
         'sporco_amd_csc_mdcpl_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_l1l1_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
         'sporco_amd_csc_ball_iter': [vp, ctypes.POINTER(AdmmParams), dptr],
+        'sporco_amd_csc_projl1_iter': [vp, ctypes.POINTER(AdmmParams), dbl, dptr],
         'sporco_amd_csc_dstep_init': [vp, vp],
         'sporco_amd_csc_dstep_md_init': [vp, vp, vp],
         'sporco_amd_csc_dstep_iter': [vp, ctypes.POINTER(DstepParams), dptr],
@@ -361,6 +362,7 @@ def load(path=None):
         'sporco_amd_prox_l1w': [ctypes.c_int, ctypes.POINTER(i64), vp, ctypes.POINTER(i64), vp, vp],
         'sporco_amd_prox_sl1l2': [ctypes.c_int, i64, i32, i64, vp, dbl, dbl, vp],
         'sporco_amd_proj_l2': [ctypes.c_int, i64, i64, i64, vp, dbl, vp],
+        'sporco_amd_proj_l1': [ctypes.c_int, i64, i64, i64, vp, dbl, vp],
         'sporco_amd_rfl2norm2': [ctypes.c_int, i32, i32, i64, vp, dptr],
     }
     for name, argtypes in sig.items():
@@ -718,6 +720,13 @@ class Solver(object):
         ``params.mu`` carries epsilon.  Returns the sums (``OUT_DFID``: the squared constraint measure)."""
         out = self._out()
         check(self._lib.sporco_amd_csc_ball_iter(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def projl1_iter(self, params, gamma):
+        """One iteration of ConvBPDNProjL1 (sporco_amd_csc_projl1_iter).  Returns the sums (``OUT_L1``:
+        the squared constraint measure; ``OUT_CGN`` / ``OUT_RGRX``: the search passes taken)."""
+        out = self._out()
+        check(self._lib.sporco_amd_csc_projl1_iter(self._h, ctypes.byref(params), float(gamma), out))
         return list(out)
 
     def inhib_setup(self, Wg, taps_rows, taps_cols, want_self, lmbda):

@@ -30,7 +30,7 @@ from .. import cnvrep as cr
 from ..fft import complex_dtype, real_dtype
 
 __all__ = ['GenericConvBPDN', 'ConvBPDN', 'ConvBPDNJoint', 'ConvBPDNGradReg',
-           'ConvBPDNMaskDcpl', 'ConvL1L1Grd', 'AddMaskSim']
+           'ConvBPDNMaskDcpl', 'ConvL1L1Grd', 'ConvBPDNProjL1', 'AddMaskSim']
 
 
 class _DeviceArray(object):
@@ -735,6 +735,117 @@ class ConvBPDN(GenericConvBPDN):
     def obfn_reg(self):
         rl1 = abs(self._wl1_scalar) * self._sums[_lib.OUT_L1]
         return (self.lmbda * rl1, rl1)
+
+
+class ConvBPDNProjL1(GenericConvBPDN):
+    r"""ConvBPDN with the l1 penalty replaced by an l1 constraint: minimise
+    (1/2)||sum_m d_m * x_m - s||_2^2 such that sum_m ||x_m||_1 <= gamma for every image (reference
+    class: sporco/admm/cbpdn.py:1220-1395) -- the counterpart of :class:`ConvMinL1InL2Ball`.
+
+    One iteration is one call of ``sporco_amd_csc_projl1_iter``: the x step of :class:`ConvBPDN`, then
+    Y = proj_l1(AX + U, gamma) with one ball per image (all pixels, channels and filters of it), whose
+    threshold comes from a few streaming reduction passes instead of a sort (csrc/csc_projl1.h), fused
+    with the relaxation, NonNegCoef / NoBndryCross and the dual update.  With an overridden step method
+    the staged steps run instead; ``ystep`` is then a device call of the projection followed by the base
+    class's.  The device-driven whole-solve loop is not used.
+
+    In scope: ``dimN = 2``, float32 / float64, ``dimK`` 0 / 1, multi-channel signals and dictionaries,
+    ``NonNegCoef``, ``NoBndryCross``, ``AutoRho``, ``RelaxParam``, ``AuxVarObj``, ``LinSolveCheck``,
+    ``Y0`` / ``U0`` (a ``Y0`` alone leaves U at zero, as in the reference), ``setdict``.  Refused with
+    ``NotImplementedError``: ``dimN`` 1 / 3, complex data, ``reducer=``, resident or device-array inputs,
+    wrapping in :class:`AddMaskSim`.
+
+    IterationStats fields: ``Iter, ObjFun, Cnstr, PrimalRsdl, DualRsdl, EpsPrimal, EpsDual, Rho,
+    XSlvRelRes, Time``.  ``ObjFun`` is the data fidelity term alone; ``Cnstr`` is ||proj_l1(g) - g||
+    with g = X, or Y under ``AuxVarObj``.
+    """
+
+    class Options(GenericConvBPDN.Options):
+        """The options of :class:`GenericConvBPDN` with ``AutoRho.RsdlTarget`` 1 (cbpdn.py:1288-1309)."""
+
+        defaults = copy.deepcopy(GenericConvBPDN.Options.defaults)
+        defaults['AutoRho'].update({'RsdlTarget': 1.0})
+
+        def __init__(self, opt=None):
+            GenericConvBPDN.Options.__init__(self, {} if opt is None else opt)
+
+    itstat_fields_objfn = ('ObjFun', 'Cnstr')
+    hdrtxt_objfn = ('Fnc', 'Cnstr')
+    hdrval_objfun = {'Fnc': 'ObjFun', 'Cnstr': 'Cnstr'}
+    _ams_refusal = ("ConvBPDNProjL1 cannot be wrapped in AddMaskSim: the impulse filter's coefficients "
+                    "would join the l1 ball")
+
+    def __init__(self, D, S, gamma, opt=None, dimK=None, dimN=2, **backend):
+        name = type(self).__name__
+        if opt is None:
+            opt = ConvBPDNProjL1.Options()
+        if dimN != 2:
+            raise NotImplementedError("%s: dimN = 2 (images)" % name)
+        if backend.get('reducer') is not None:
+            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
+        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, S)):
+            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
+        if np.iscomplexobj(D) or np.iscomplexobj(S):
+            raise NotImplementedError("%s handles real-valued D and S" % name)
+        super(ConvBPDNProjL1, self).__init__(D, S, opt, dimK=dimK, dimN=dimN, **backend)
+        self.gamma = self.dtype.type(gamma)
+        if not self.gamma >= 0:
+            raise ValueError("gamma must not be negative")
+        #: search passes of the last iteration: (y step, constraint measure)
+        self.search_passes = (0, 0)
+
+    def uinit(self, ushape):
+        """Zeros, also when a ``Y0`` is given (cbpdn.py:1359-1369)."""
+        return np.zeros(ushape, dtype=self.dtype)
+
+    def _device_loop_ok(self):
+        return False
+
+    def iteration(self):
+        if not self._fused_ok():
+            return super(GenericConvBPDN, self).iteration()
+        self._sums = self._dev.projl1_iter(self._params(), float(self.gamma))
+        self.search_passes = (int(self._sums[_lib.OUT_CGN]), int(self._sums[_lib.OUT_RGRX]))
+        self._u_scale = 1.0
+        self._touch(_lib.VAR_X, _lib.VAR_Y, _lib.VAR_U, _lib.VAR_XF, _lib.VAR_AX, _lib.VAR_YPREV)
+        self._set_xrrs()
+        if not self._needs_residuals():
+            return None
+        self.timer.stop('solve_wo_rsdl')
+        res = self.compute_residuals()
+        self.timer.start('solve_wo_rsdl')
+        return res
+
+    def _axes(self):
+        return tuple(self.cri.axisN) + (self.cri.axisC, self.cri.axisM)
+
+    def ystep(self):
+        """Y = proj_l1(AX + U, gamma) over the spatial, channel and filter axes, then NonNegCoef /
+        NoBndryCross (cbpdn.py:1373-1381) -- the staged form."""
+        from .. import prox
+        Y = prox.proj_l1(self.AX + self.U, float(self.gamma), axis=self._axes())
+        # (the base class's device step forms Y from AX + U itself; here Y is the projection, so the two
+        # options are applied to it as cbpdn.py:297-311 does)
+        if self.opt['NonNegCoef']:
+            Y[Y < 0.0] = 0.0
+        if self.opt['NoBndryCross']:
+            for n in range(self.cri.dimN):
+                Y[(slice(None),) * n + (slice(1 - self.D.shape[n], None),)] = 0.0
+        self.Y = Y
+
+    def eval_objfn(self):
+        """The data fidelity term and the constraint measure ||proj_l1(g) - g|| (cbpdn.py:1385-1395)."""
+        dfd = self.obfn_dfd()
+        if self._fused_ok():
+            cns = float(np.sqrt(self._sums[_lib.OUT_L1]))
+        else:
+            from .. import prox
+            g = self.Y if self.opt['gEvalY'] else self.X
+            cns = float(np.linalg.norm(prox.proj_l1(g, float(self.gamma), axis=self._axes()) - g))
+        return (dfd, cns)
+
+
+ConvBPDNProjL1._fused_base = ConvBPDNProjL1
 
 
 class ConvBPDNJoint(ConvBPDN):

@@ -590,6 +590,15 @@ int sporco_amd_csc_ball_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p
     SA_API_END
 }
 
+int sporco_amd_csc_projl1_iter(sporco_amd_csc_t h, const sporco_amd_admm_params *p, double gamma,
+                               double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_HANDLE_ANY(h);
+    SA_REQUIRE(p && out, "null argument");
+    h->impl->projl1_iter(*p, gamma, stats_buf(h), out);
+    SA_API_END
+}
+
 int sporco_amd_csc_inhib_setup(sporco_amd_csc_t h, const double *Wg, int32_t Ng,
                                const double *taps_rows, int32_t ntaps_rows, const double *taps_cols,
                                int32_t ntaps_cols, int32_t want_self, double lmbda) {

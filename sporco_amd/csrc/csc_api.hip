@@ -31,7 +31,9 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "pd_solve",         "pd_recon",
                                     "l1l1_y0step",      "l1l1_dual",
                                     "ball_norms",       "ball_y0step",
-                                    "pdl1_solve",       "pdl1_dual"};
+                                    "pdl1_solve",       "pdl1_dual",
+                                    "projl1_search",    "projl1_apply",
+                                    "projl1_pass0",     "projl1_cnstr"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -441,6 +443,7 @@ template <typename T> struct Csc : CscBase {
         pd_release();
         l1l1_release();
         pdl1_release();
+        projl1_release();
         big_free(gemit);
         if (part_vpost) (void)hipFree(part_vpost);
         big_free(cols_out[0]);
@@ -641,6 +644,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_pd.inc"
 #include "api_l1l1.inc"
 #include "api_pdl1.inc"
+#include "api_projl1.inc"
 };
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

@@ -22,6 +22,7 @@
 #include "csc_pd.h"
 #include "csc_pdl1.h"
 #include "csc_pgm.h"
+#include "csc_projl1.h"
 #include "csc_rows.h"
 #include "csc_rtv.h"
 #include "csc_tv.h"
@@ -105,6 +106,10 @@ enum ProfSlot {
     PS_BALL_Y0STEP,             // ... relax + projection onto the l2 balls + u step of block 0
     PS_PDL1_SOLVE,              // ConvProdDictL1L1Grd: the eigen-channel diagonal-plus-rank-one x step (csc_pdl1.h)
     PS_PDL1_DUAL,               // ... the norm of A^T u through B in one read pass
+    PS_PROJL1_SEARCH,           // ConvBPDNProjL1: the threshold search passes of the l1-ball projection (csc_projl1.h)
+    PS_PROJL1_APPLY,            // ... relax + shrink + u step
+    PS_PROJL1_PASS0,            // ... the first search pass of the y step alone: every image, whole arrays
+    PS_PROJL1_CNSTR,            // ... the constraint measure's read pass
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -231,6 +236,7 @@ struct CscBase {
     virtual void mdcpl_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void l1l1_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
     virtual void ball_iter(const sporco_amd_admm_params &p, double *out_dev) = 0;
+    virtual void projl1_iter(const sporco_amd_admm_params &p, double gamma, double *out_dev, double *out_host) = 0;
     virtual void dstep_init(const void *Y0) = 0;
     virtual void dstep_md_init(const void *Y0, const void *S) = 0;
     virtual void dstep_iter(const sporco_amd_dstep_params &p, double *out_dev) = 0;

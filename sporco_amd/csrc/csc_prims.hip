@@ -227,6 +227,31 @@ void prim_proj_l2(int64_t outer, int64_t C, int64_t inner, const void *v, double
     SA_HIP(hipMemcpy(out, dout.p, sizeof(T) * n, hipMemcpyDeviceToHost));
 }
 
+// proj_l1: the search and the apply pass of csc_projl1.h on a plain array
+template <typename T>
+void prim_proj_l1(int64_t outer, int64_t P, int64_t inner, const void *v, double gamma, void *out) {
+    const int64_t n = outer * P * inner;
+    const ProjL1Geom g = projl1_geom(sizeof(T), outer, P, inner);
+    DevBuf dv(sizeof(T) * n), dout(sizeof(T) * n), dws(sizeof(double) * g.workspace_doubles()),
+        dpart(sizeof(double) * kMaxPartialBlocks * 8);
+    SA_HIP(hipMemcpy(dv.p, v, sizeof(T) * n, hipMemcpyHostToDevice));
+    ProjL1Args<T> a;
+    a.x = dv.as<T>();
+    a.out = dout.as<T>();
+    a.gamma = gamma;
+    a.ws = dws.as<double>();
+    projl1_reset(nullptr, a.ws, g);
+    double cnt[2] = {1.0, 0.0};
+    for (int round = 0; cnt[0] != 0.0; ++round) {
+        SA_REQUIRE(round < 64, "proj_l1: the threshold search did not end");
+        launch_projl1_search<T>(nullptr, a, g, round == 0 ? 4 : 2, round == 0);
+        SA_HIP(hipMemcpy(cnt, projl1_counter(a.ws, g), sizeof(cnt), hipMemcpyDeviceToHost));
+    }
+    launch_projl1_apply<T>(nullptr, a, g, dpart.as<double>());
+    SA_HIP(hipDeviceSynchronize());
+    SA_HIP(hipMemcpy(out, dout.p, sizeof(T) * n, hipMemcpyDeviceToHost));
+}
+
 template <typename T> void prim_rfl2norm2(int H, int W, int64_t P, const void *xf, double *out) {
     const int64_t npix = (int64_t)H * (W / 2 + 1);
     DevBuf dx(sizeof(cx<T>) * npix * P), dpart(sizeof(double) * kMaxPartialBlocks),
@@ -385,6 +410,14 @@ int sporco_amd_proj_l2(int dtype, int64_t outer, int64_t C, int64_t inner, const
     SA_API_BEGIN
     SA_REQUIRE(v && out && outer >= 1 && C >= 1 && inner >= 1 && gamma >= 0.0, "bad argument");
     SA_DISPATCH(dtype, prim_proj_l2, outer, C, inner, v, gamma, out)
+    SA_API_END
+}
+
+int sporco_amd_proj_l1(int dtype, int64_t outer, int64_t P, int64_t inner, const void *v, double gamma,
+                       void *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(v && out && outer >= 1 && P >= 1 && inner >= 1 && gamma >= 0.0, "bad argument");
+    SA_DISPATCH(dtype, prim_proj_l1, outer, P, inner, v, gamma, out)
     SA_API_END
 }
 

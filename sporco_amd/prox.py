@@ -1,8 +1,8 @@
 """Device proximal operators with the signatures of ``sporco.prox``.
 
 ``prox_l1`` (sporco/prox/_lp.py:144-183), ``prox_sl1l2``
-(sporco/prox/_l21.py:51-88) and ``proj_l2`` (sporco/prox/_lp.py:334-340) for
-real arrays and scalar parameters; inside the solvers the same arithmetic runs
+(sporco/prox/_l21.py:51-88), ``proj_l2`` (sporco/prox/_lp.py:334-340) and
+``proj_l1`` (sporco/prox/_l1proj.py:24-154) for real arrays and scalar parameters; inside the solvers the same arithmetic runs
 fused into the ADMM / PGM epilogue kernels, where weight arrays are supported.
 """
 
@@ -109,6 +109,52 @@ def proj_l2(v, gamma, axis=None):
     if v.size:
         _lib.check(_lib.lib().sporco_amd_proj_l2(_lib.dtype_code(v.dtype), outer, C, inner, _lib._ptr(v),
                                                  float(gamma), _lib._ptr(out)))
+    return out
+
+
+def proj_l1(v, gamma, axis=None):
+    """Euclidean projection onto the l1 ball of radius ``gamma``, the norm taken over ``axis``: None
+    (the whole array), an int, or a tuple of axes (sporco/prox/_l1proj.py:24-154, without ``method``:
+    the threshold comes from streaming reductions on the device, csrc/csc_projl1.h).  A vector inside
+    its ball is returned as it is.  When the axes that are NOT summed over are a single axis the array
+    is projected in place of its layout; otherwise those axes are moved to the front on the host."""
+    if np.ndim(gamma) != 0:
+        raise NotImplementedError("array-valued parameters are handled inside the solvers only")
+    if not float(gamma) >= 0.0:
+        raise ValueError("gamma must not be negative")
+    v = _real(v)
+    if v.size == 0:
+        return v
+    if axis is None:
+        axes = tuple(range(v.ndim))
+    elif isinstance(axis, (int, np.integer)):
+        axes = (int(axis) % v.ndim,)
+    elif isinstance(axis, (tuple, list)) and len(axis) > 0 and \
+            all(isinstance(a, (int, np.integer)) for a in axis):
+        axes = tuple(sorted(set(int(a) % v.ndim for a in axis)))
+    else:
+        raise NotImplementedError("axis must be None, an int or a tuple of ints")
+    rest = tuple(k for k in range(v.ndim) if k not in axes)
+    moved = None
+    if len(rest) == 0:
+        outer, P, inner = 1, 1, v.size
+        w = v
+    elif len(rest) == 1:
+        k = rest[0]
+        outer = int(np.prod(v.shape[:k], dtype=np.int64))
+        P = int(v.shape[k])
+        inner = int(np.prod(v.shape[k + 1:], dtype=np.int64))
+        w = v
+    else:
+        moved = rest + axes
+        w = np.ascontiguousarray(np.transpose(v, moved))
+        P = int(np.prod([v.shape[k] for k in rest], dtype=np.int64))
+        outer, inner = 1, w.size // P
+    out = np.empty_like(w)
+    _lib.check(_lib.lib().sporco_amd_proj_l1(_lib.dtype_code(w.dtype), outer, P, inner, _lib._ptr(w),
+                                             float(gamma), _lib._ptr(out)))
+    if moved is not None:
+        out = np.ascontiguousarray(np.transpose(out, np.argsort(moved)))
     return out
 
 

@@ -44,6 +44,9 @@ def main():
     from conftest import use_backend
     use_backend('hostsim')
     import sporco  # noqa: F401  (the reference package: everything not aliased comes from it)
+    if any(a.endswith('test_prox.py') for a in sys.argv[1:]):
+        # (the reference's tests/test_prox.py against this package's prox module: what it lacks fails)
+        ALIASES['sporco.prox'] = 'sporco_amd.prox'
     for ref_name, our_name in ALIASES.items():
         mod = importlib.import_module(our_name)
         importlib.import_module(ref_name.rsplit('.', 1)[0])
