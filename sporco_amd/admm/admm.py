@@ -44,6 +44,23 @@ def refuse_step_overrides(obj, names=STEP_HOOKS):
                 break
 
 
+def refuse_backend_extras(name, D, S, dimN, backend, dims=(2,), dim_note='', shard_note='', B=None):
+    """For solver classes that take host arrays of real data on one device: anything else among
+    the constructor's arguments raises.  ``dim_note`` is the class's own sentence on the ``dimN``
+    it serves, ``shard_note`` what it has to add about image shards; ``B`` is the standard
+    dictionary of the product-dictionary classes."""
+    arrays = (D, S) if B is None else (D, B, S)
+    if dimN not in dims:
+        raise NotImplementedError("%s: %s" % (name, dim_note))
+    if backend.get('reducer') is not None:
+        raise NotImplementedError("%s: no image sharding (reducer=)%s" % (name, shard_note))
+    if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in arrays):
+        raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
+    if any(np.iscomplexobj(a) for a in arrays):
+        raise NotImplementedError("%s handles real-valued %s"
+                                  % (name, "D and S" if B is None else "D, B and S"))
+
+
 class ADMM(common.IterativeSolver):
     r"""Base class: minimise f(x) + g(y) subject to Ax + By = c."""
 

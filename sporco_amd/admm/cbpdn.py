@@ -422,8 +422,14 @@ class GenericConvBPDN(admm.ADMMEqual):
             self._sums = self._dev.admm_iter(p)
         else:
             self._sums = self._reducer.admm_iter(self._dev, p)
+        return self._finish_device_iteration((_lib.VAR_X, _lib.VAR_Y, _lib.VAR_U, _lib.VAR_XF))
+
+    def _finish_device_iteration(self, touched):
+        """What follows the one device call of an iteration, with its sums in ``_sums``: the
+        pending scale of U is spent, the host copies of the ``touched`` arrays are stale, and the
+        residuals (or None, when nobody needs them) are formed outside the 'solve_wo_rsdl' timer."""
         self._u_scale = 1.0
-        self._touch(_lib.VAR_X, _lib.VAR_Y, _lib.VAR_U, _lib.VAR_XF)
+        self._touch(*touched)
         self._set_xrrs()
         if not self._needs_residuals():
             return None
@@ -776,17 +782,9 @@ class ConvBPDNProjL1(GenericConvBPDN):
                     "would join the l1 ball")
 
     def __init__(self, D, S, gamma, opt=None, dimK=None, dimN=2, **backend):
-        name = type(self).__name__
         if opt is None:
             opt = ConvBPDNProjL1.Options()
-        if dimN != 2:
-            raise NotImplementedError("%s: dimN = 2 (images)" % name)
-        if backend.get('reducer') is not None:
-            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
-        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, S)):
-            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
-        if np.iscomplexobj(D) or np.iscomplexobj(S):
-            raise NotImplementedError("%s handles real-valued D and S" % name)
+        admm.refuse_backend_extras(type(self).__name__, D, S, dimN, backend, dim_note="dimN = 2 (images)")
         super(ConvBPDNProjL1, self).__init__(D, S, opt, dimK=dimK, dimN=dimN, **backend)
         self.gamma = self.dtype.type(gamma)
         if not self.gamma >= 0:
@@ -806,15 +804,8 @@ class ConvBPDNProjL1(GenericConvBPDN):
             return super(GenericConvBPDN, self).iteration()
         self._sums = self._dev.projl1_iter(self._params(), float(self.gamma))
         self.search_passes = (int(self._sums[_lib.OUT_CGN]), int(self._sums[_lib.OUT_RGRX]))
-        self._u_scale = 1.0
-        self._touch(_lib.VAR_X, _lib.VAR_Y, _lib.VAR_U, _lib.VAR_XF, _lib.VAR_AX, _lib.VAR_YPREV)
-        self._set_xrrs()
-        if not self._needs_residuals():
-            return None
-        self.timer.stop('solve_wo_rsdl')
-        res = self.compute_residuals()
-        self.timer.start('solve_wo_rsdl')
-        return res
+        return self._finish_device_iteration((_lib.VAR_X, _lib.VAR_Y, _lib.VAR_U, _lib.VAR_XF, _lib.VAR_AX,
+                                              _lib.VAR_YPREV))
 
     def _axes(self):
         return tuple(self.cri.axisN) + (self.cri.axisC, self.cri.axisM)
@@ -926,7 +917,47 @@ class ConvBPDNJoint(ConvBPDN):
         return (self.lmbda * rl1 + self.mu * rl21, rl1, rl21)
 
 
-class ConvBPDNGradReg(ConvBPDN):
+class _GradWeight(object):
+    """The ``GradWeight`` option of the gradient-regularised classes (cbpdn.py:1059-1073,
+    :2564-2595): parsed into ``Wgrd``; one weight per filter is uploaded to the handle, a scalar
+    folds into mu."""
+
+    def _set_grad_weight(self, gw, dimN):
+        if hasattr(gw, 'ndim') and np.ndim(gw) > 0:
+            # one weight per filter, broadcast along the filter axis (cbpdn.py:1134-1137, :2649-2653)
+            self.Wgrd = np.asarray(np.asarray(gw).reshape((1,) * (dimN + 2) + np.shape(gw)),
+                                   dtype=self.dtype)
+        else:
+            self.Wgrd = np.asarray(gw, dtype=self.dtype)
+
+    @property
+    def GHGf(self):
+        """Wgrd * sum_i |G_i|^2 on the half spectrum (cbpdn.py:1141-1143); host-side
+        convenience, the kernels evaluate it from two separable tables."""
+        H, W = self.cri.Nv
+        gh = (2.0 - 2.0 * np.cos(2.0 * np.pi * np.arange(H) / H)) if H > 1 else np.ones(1)
+        gw = (2.0 - 2.0 * np.cos(2.0 * np.pi * np.arange(W // 2 + 1) / W)) if W > 1 \
+            else np.ones(1)
+        g = (gh[:, np.newaxis] + gw[np.newaxis, :]).reshape(H, W // 2 + 1, 1, 1, 1)
+        return self.Wgrd * g.astype(self.dtype)
+
+    def _upload_weights(self):
+        super(_GradWeight, self)._upload_weights()
+        if self.Wgrd.size == 1:
+            self._wg_scalar = float(self.Wgrd.ravel()[0])
+            self._dev.set_grad_weight(None)
+        else:
+            if self.Wgrd.size != self.cri.M:
+                raise ValueError("GradWeight must be a scalar or hold one weight per filter")
+            self._wg_scalar = 1.0
+            self._dev.set_grad_weight(self.Wgrd.ravel())
+
+    def _mu_eff(self):
+        # a scalar GradWeight folds into mu: mu * (w GHGf)
+        return float(self.mu) * self._wg_scalar
+
+
+class ConvBPDNGradReg(_GradWeight, ConvBPDN):
     r"""ConvBPDN with an l2 penalty on the gradient of the coefficient maps,
     (mu/2) sum_i sum_m w_m ||G_i x_m||_2^2 (reference class:
     sporco/admm/cbpdn.py:992-1214).  The gradient term enters the X step only:
@@ -966,41 +997,9 @@ class ConvBPDNGradReg(ConvBPDN):
             opt = ConvBPDNGradReg.Options()
         self.set_dtype(opt, S.dtype)
         self.mu = self.dtype.type(mu)
-        gw = opt['GradWeight']
-        if hasattr(gw, 'ndim') and np.ndim(gw) > 0:
-            # one weight per filter, broadcast along the filter axis (cbpdn.py:1134-1137)
-            self.Wgrd = np.asarray(np.asarray(gw).reshape((1,) * (dimN + 2) + np.shape(gw)),
-                                   dtype=self.dtype)
-        else:
-            self.Wgrd = np.asarray(gw, dtype=self.dtype)
+        self._set_grad_weight(opt['GradWeight'], dimN)
         super(ConvBPDNGradReg, self).__init__(D, S, lmbda, opt, dimK=dimK, dimN=dimN,
                                               **backend)
-
-    @property
-    def GHGf(self):
-        """Wgrd * sum_i |G_i|^2 on the half spectrum (cbpdn.py:1141-1143); host-side
-        convenience, the kernels evaluate it from two separable tables."""
-        H, W = self.cri.Nv
-        gh = (2.0 - 2.0 * np.cos(2.0 * np.pi * np.arange(H) / H)) if H > 1 else np.ones(1)
-        gw = (2.0 - 2.0 * np.cos(2.0 * np.pi * np.arange(W // 2 + 1) / W)) if W > 1 \
-            else np.ones(1)
-        g = (gh[:, np.newaxis] + gw[np.newaxis, :]).reshape(H, W // 2 + 1, 1, 1, 1)
-        return self.Wgrd * g.astype(self.dtype)
-
-    def _upload_weights(self):
-        super(ConvBPDNGradReg, self)._upload_weights()
-        if self.Wgrd.size == 1:
-            self._wg_scalar = float(self.Wgrd.ravel()[0])
-            self._dev.set_grad_weight(None)
-        else:
-            if self.Wgrd.size != self.cri.M:
-                raise ValueError("GradWeight must be a scalar or hold one weight per filter")
-            self._wg_scalar = 1.0
-            self._dev.set_grad_weight(self.Wgrd.ravel())
-
-    def _mu_eff(self):
-        # a scalar GradWeight folds into mu: mu * (w GHGf)
-        return float(self.mu) * self._wg_scalar
 
     def _flags(self):
         return super(ConvBPDNGradReg, self)._flags() | _lib.FLAG_GRADREG
@@ -1226,15 +1225,7 @@ class ConvBPDNMaskDcpl(ConvBPDN):
         self._sums = self._device_iteration(p)
         if self._reducer is not None:
             self._sums = self._reducer.sum(self._sums)
-        self._u_scale = 1.0
-        self._touch(_lib.VAR_X, _lib.VAR_Y, _lib.VAR_U, _lib.VAR_XF)
-        self._set_xrrs()
-        if not self._needs_residuals():
-            return None
-        self.timer.stop('solve_wo_rsdl')
-        res = self.compute_residuals()
-        self.timer.start('solve_wo_rsdl')
-        return res
+        return self._finish_device_iteration((_lib.VAR_X, _lib.VAR_Y, _lib.VAR_U, _lib.VAR_XF))
 
     def _device_iteration(self, p):
         """The one device call of an iteration; returns the sums."""
@@ -1264,7 +1255,7 @@ class ConvBPDNMaskDcpl(ConvBPDN):
         return super(ConvBPDNMaskDcpl, self).reconstruct(X)
 
 
-class ConvL1L1Grd(ConvBPDNMaskDcpl):
+class ConvL1L1Grd(_GradWeight, ConvBPDNMaskDcpl):
     r"""Convolutional sparse coding with an l1 data fidelity term under a mask, an l1 penalty on the
     coefficient maps and an l2 penalty on their gradient: minimise
     ||W(sum_m d_m * x_m - s)||_1 + lambda sum_m ||x_m||_1 + (mu/2) sum_i sum_m w_m ||G_i x_m||_2^2
@@ -1302,46 +1293,15 @@ class ConvL1L1Grd(ConvBPDNMaskDcpl):
     hdrtxt_objfn = ('Fnc', 'DFid', u'Regℓ1', u'Regℓ2∇')
     hdrval_objfun = {'Fnc': 'ObjFun', 'DFid': 'DFid', u'Regℓ1': 'RegL1', u'Regℓ2∇': 'RegGrad'}
 
-    GHGf = ConvBPDNGradReg.GHGf
-
     def __init__(self, D, S, lmbda, mu, W=None, opt=None, dimK=None, dimN=2, **backend):
-        name = type(self).__name__
         if opt is None:
             opt = ConvL1L1Grd.Options()
-        if dimN != 2:
-            raise NotImplementedError("%s: dimN = 2 (images); the gradient term is the "
-                                      "two-dimensional one" % name)
-        if backend.get('reducer') is not None:
-            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
-        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, S)):
-            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
-        if np.iscomplexobj(D) or np.iscomplexobj(S):
-            raise NotImplementedError("%s handles real-valued D and S" % name)
+        admm.refuse_backend_extras(type(self).__name__, D, S, dimN, backend,
+                                   dim_note="dimN = 2 (images); the gradient term is the two-dimensional one")
         self.set_dtype(opt, S.dtype)
         self.mu = self.dtype.type(mu)
-        gw = opt['GradWeight']
-        if hasattr(gw, 'ndim') and np.ndim(gw) > 0:
-            # one weight per filter, broadcast along the filter axis (cbpdn.py:2649-2653)
-            self.Wgrd = np.asarray(np.asarray(gw).reshape((1,) * (dimN + 2) + np.shape(gw)),
-                                   dtype=self.dtype)
-        else:
-            self.Wgrd = np.asarray(gw, dtype=self.dtype)
+        self._set_grad_weight(opt['GradWeight'], dimN)
         super(ConvL1L1Grd, self).__init__(D, S, lmbda, W, opt, dimK=dimK, dimN=dimN, **backend)
-
-    def _upload_weights(self):
-        super(ConvL1L1Grd, self)._upload_weights()
-        if self.Wgrd.size == 1:
-            self._wg_scalar = float(self.Wgrd.ravel()[0])
-            self._dev.set_grad_weight(None)
-        else:
-            if self.Wgrd.size != self.cri.M:
-                raise ValueError("GradWeight must be a scalar or hold one weight per filter")
-            self._wg_scalar = 1.0
-            self._dev.set_grad_weight(self.Wgrd.ravel())
-
-    def _mu_eff(self):
-        # a scalar GradWeight folds into mu: mu * (w GHGf)
-        return float(self.mu) * self._wg_scalar
 
     def __getstate__(self):
         raise NotImplementedError("%s: pickling is not offered" % type(self).__name__)
@@ -1418,17 +1378,9 @@ class ConvMinL1InL2Ball(ConvBPDNMaskDcpl):
     hdrval_objfun = {'Fnc': 'ObjFun', 'Cnstr': 'Cnstr'}
 
     def __init__(self, D, S, epsilon, opt=None, dimK=None, dimN=2, **backend):
-        name = type(self).__name__
         if opt is None:
             opt = ConvMinL1InL2Ball.Options()
-        if dimN != 2:
-            raise NotImplementedError("%s: dimN = 2 (images)" % name)
-        if backend.get('reducer') is not None:
-            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
-        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, S)):
-            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
-        if np.iscomplexobj(D) or np.iscomplexobj(S):
-            raise NotImplementedError("%s handles real-valued D and S" % name)
+        admm.refuse_backend_extras(type(self).__name__, D, S, dimN, backend, dim_note="dimN = 2 (images)")
         self.set_dtype(opt, S.dtype)
         self.epsilon = self.dtype.type(epsilon)
         if not self.epsilon >= 0:

@@ -80,17 +80,9 @@ class ConvBPDNScalarTV(admm.ADMM):
         name = type(self).__name__
         if opt is None:
             opt = ConvBPDNScalarTV.Options()
-        if dimN != 2:
-            raise NotImplementedError("%s: dimN = 2 (images); the stencil kernels know two "
-                                      "spatial axes" % name)
-        if backend.get('reducer') is not None:
-            raise NotImplementedError("%s: no image sharding (reducer=): the gradient stencil "
-                                      "crosses the shard borders" % name)
-        if backend.get('resident') or not isinstance(S, np.ndarray) or \
-                not isinstance(D, np.ndarray):
-            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
-        if np.iscomplexobj(D) or np.iscomplexobj(S):
-            raise NotImplementedError("%s handles real-valued D and S" % name)
+        admm.refuse_backend_extras(name, D, S, dimN, backend,
+                                   dim_note="dimN = 2 (images); the stencil kernels know two spatial axes",
+                                   shard_note=": the gradient stencil crosses the shard borders")
         if opt['NonNegCoef'] or opt['NoBndryCross']:
             raise NotImplementedError("%s: NonNegCoef / NoBndryCross are not offered (the "
                                       "reference's TV y step ignores them)" % name)

@@ -26,6 +26,7 @@ import copy
 
 import numpy as np
 
+from . import admm
 from . import cbpdn
 from .. import _lib
 from .. import cnvrep as cr
@@ -33,6 +34,7 @@ from .. import cnvrep as cr
 __all__ = ['ConvProdDictBPDN', 'ConvProdDictBPDNJoint', 'ConvProdDictL1L1Grd', 'ConvProdDictL1L1GrdJoint']
 
 MAX_CB = 16      # csrc/csc_pd.h kPdMaxCb
+_DIM_NOTE = "dimN = 2 (images); the channel mix of the x step is built on the two-dimensional transforms"
 
 
 class ConvProdDictBPDN(cbpdn.ConvBPDN):
@@ -66,15 +68,7 @@ class ConvProdDictBPDN(cbpdn.ConvBPDN):
         name = type(self).__name__
         if opt is None:
             opt = ConvProdDictBPDN.Options()
-        if dimN != 2:
-            raise NotImplementedError("%s: dimN = 2 (images); the channel mix of the x step is built "
-                                      "on the two-dimensional transforms" % name)
-        if backend.get('reducer') is not None:
-            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
-        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, B, S)):
-            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
-        if np.iscomplexobj(D) or np.iscomplexobj(B) or np.iscomplexobj(S):
-            raise NotImplementedError("%s handles real-valued D, B and S" % name)
+        admm.refuse_backend_extras(name, D, S, dimN, backend, dim_note=_DIM_NOTE, B=B)
         # D acts on X B^T: the coefficient maps have as many channels as B has columns
         # (pdcsc.py:83-93)
         self.cri = cr.CSC_ConvRepIndexing(D, S, dimK=dimK, dimN=dimN)
@@ -263,15 +257,7 @@ class ConvProdDictL1L1Grd(cbpdn.ConvL1L1Grd):
         name = type(self).__name__
         if opt is None:
             opt = type(self).Options()
-        if dimN != 2:
-            raise NotImplementedError("%s: dimN = 2 (images); the channel mix of the x step is built "
-                                      "on the two-dimensional transforms" % name)
-        if backend.get('reducer') is not None:
-            raise NotImplementedError("%s: no image sharding (reducer=)" % name)
-        if backend.get('resident') or not all(isinstance(a, np.ndarray) for a in (D, B, S)):
-            raise NotImplementedError("%s takes host arrays and returns host arrays" % name)
-        if np.iscomplexobj(D) or np.iscomplexobj(B) or np.iscomplexobj(S):
-            raise NotImplementedError("%s handles real-valued D, B and S" % name)
+        admm.refuse_backend_extras(name, D, S, dimN, backend, dim_note=_DIM_NOTE, B=B)
         # the reference hands its base class S B so that the arrays get Cb channels, then corrects the
         # shapes (pdcsc.py:363-403); here the indexing is built on S and the coefficient maps' channel
         # count is set, as in ConvProdDictBPDN

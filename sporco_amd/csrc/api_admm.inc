@@ -1,6 +1,61 @@
 // api_admm.inc -- member functions of template Csc<T> (csc_api.hip includes this file INSIDE the
 // class body): ADMM ConvBPDN family: fused and staged iterations.
     // ---- ADMM --------------------------------------------------------------------
+    // The tables of the iterated Sherman-Morrison solve (multi-channel dictionary): allocated on
+    // first use, rebuilt when they were built for another system than the one asked for.  The
+    // system is (rho, the gradient diagonal gt); mu_key names the diagonal -- the mu it was built
+    // with, -1 for none -- so that a handle serving several solver kinds in turn (a gradient-
+    // regularised solve, then a mask-decoupled one with rho = 1) never reuses the other kind's
+    // tables.  A new dictionary or GradWeight clears ism_valid.  (Without gt the kernel does not
+    // read W.)
+    void ism_tables(double rho, const GradTerm<T> *gt, double mu_key) {
+        if (!ism_gam) {
+            SA_HIP(hipMalloc((void **)&ism_gam, sizeof(cx<T>) * npix * Cd * K));
+            SA_HIP(hipMalloc((void **)&ism_del, sizeof(cx<T>) * npix * Cd));
+            SA_HIP(hipMalloc((void **)&ism_mm, sizeof(cx<T>) * npix * Cd * Cd));
+        }
+        if (ism_valid && ism_rho == rho && ism_mu == mu_key) return;
+        ProfScope ps(prof, PS_OTHER);
+        launch_ism_setup<T>(st, cv(SPORCO_AMD_VAR_DF), ism_gam, ism_del, ism_mm, npix, Cd, K, (T)rho, gt, W);
+        ism_valid = true;
+        ism_rho = rho;
+        ism_mu = mu_key;
+    }
+
+    // The generic chain's solve of (D^H D + rho I [+ gt]) xf = conj(Df) sf + rho b in the natural
+    // layout: Sherman-Morrison, or its iterated form for a multi-channel dictionary (cbpdn.py:277-279;
+    // with gt the identity term is the diagonal mu wg GHGf + rho, :1181-1184).  Partials to part_a
+    // (finalize_solve); returns the number of blocks that wrote them.
+    int generic_solve(const cx<T> *b, cx<T> *xf, const cx<T> *sf, T rho, bool obj, bool xr,
+                      const GradTerm<T> *gt, double mu_key) {
+        if (Cd > 1) ism_tables((double)rho, gt, mu_key);
+        ProfScope ps(prof, PS_SM_SOLVE);
+        if (Cd > 1)
+            return launch_ism_solve<T>(st, b, xf, cv(SPORCO_AMD_VAR_DF), sf, ism_gam, ism_del, ism_mm, rho, npix,
+                                       Cd, N, K, W, obj, xr, part_a, gt);
+        return launch_sm_solve<T>(st, b, xf, cv(SPORCO_AMD_VAR_DF), sf, gram, rho, npix, CN, K, W, obj, xr, part_a,
+                                  gt);
+    }
+
+    // The column pass of the generic chain as one kernel: column transform, Sherman-Morrison solve
+    // and inverse column transform of a (wf, cn) tile in LDS (fft.h fft_cols_sm), two passes over
+    // the spectrum instead of six; the data fidelity -> out_dev.  The Xf buffer is left holding the
+    // column-inverse-transformed solution (the caller marks it xf_tiled).
+    void run_cols_sm(const sporco_amd_admm_params &p, bool obj, double *out_dev) {
+        if (!part_cs) SA_HIP(hipMalloc((void **)&part_cs, sizeof(double) * (int64_t)Wf * CN));
+        int64_t nt;
+        {
+            ProfScope ps(prof, PS_SM_SOLVE);
+            nt = fft_cols_sm<T>(st, planH, cv(SPORCO_AMD_VAR_XF), cv(SPORCO_AMD_VAR_DF), cv(SPORCO_AMD_VAR_SF), gram,
+                                (T)p.rho, Wf, CN, K, W, obj, part_cs, sw.cols_sm_force_slab, &cols_sm_form);
+        }
+        if (obj) {
+            const int slots[1] = {SPORCO_AMD_OUT_DFID};
+            const double scales[1] = {1.0 / ((double)H * W)};
+            finalize(part_cs, (int)nt, 1, 1, slots, scales, out_dev);
+        }
+    }
+
     // X-step: Xf = SM(rfftn(Y - s U)), X = irfftn(Xf); objective / check sums -> out_dev
     // (gv: the iterate as the single array V = AX + U, produced with the threshold gv_thr_in --
     // the generic row transform derives Y - s U from it; admm_iter)
@@ -65,68 +120,15 @@
         xf_tiled = false;
         const bool obj = (p.flags & F_OBJ) && !(p.flags & F_FEVAL_Y);
         const bool xr = p.flags & F_XRRS;
-        if (!cols_sm_ok(p)) fwd2(Y, U, (T)p.u_scale, Xf, P, vf);
-        if (Cd > 1) {
-            // multi-channel dictionary: iterated Sherman-Morrison (cbpdn.py:277-279)
-            // (ConvBPDNGradReg: the identity term becomes the diagonal mu wg GHGf + rho,
-            // cbpdn.py:1181-1184; AddMaskSim and ConvBPDNJoint differ in the y step only)
-            GradTerm<T> gtm;
-            if (gradreg) gtm = grad_term(p.mu);
-            const double ism_mu_now = gradreg ? p.mu : -1.0;
-            if (!ism_gam) {
-                SA_HIP(hipMalloc((void **)&ism_gam, sizeof(cx<T>) * npix * Cd * K));
-                SA_HIP(hipMalloc((void **)&ism_del, sizeof(cx<T>) * npix * Cd));
-                SA_HIP(hipMalloc((void **)&ism_mm, sizeof(cx<T>) * npix * Cd * Cd));
-            }
-            if (!ism_valid || ism_rho != p.rho || ism_mu != ism_mu_now) {
-                ProfScope ps(prof, PS_OTHER);
-                launch_ism_setup<T>(st, cv(SPORCO_AMD_VAR_DF), ism_gam, ism_del, ism_mm, npix, Cd, K,
-                                    (T)p.rho, gradreg ? &gtm : nullptr, W);
-                ism_valid = true;
-                ism_rho = p.rho;
-                ism_mu = ism_mu_now;
-            }
-            int nbm;
-            {
-                ProfScope ps(prof, PS_SM_SOLVE);
-                nbm = launch_ism_solve<T>(st, Xf, Xf, cv(SPORCO_AMD_VAR_DF), cv(SPORCO_AMD_VAR_SF),
-                                          ism_gam, ism_del, ism_mm, (T)p.rho, npix, Cd, N, K, W, obj, xr,
-                                          part_a, gradreg ? &gtm : nullptr);
-            }
-            if (obj || xr) {
-                const int slots[5] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_XRRS_D2,
-                                      SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2,
-                                      SPORCO_AMD_OUT_RGR};
-                const double scales[5] = {1.0 / ((double)H * W), 1.0, 1.0, 1.0, 1.0 / ((double)H * W)};
-                const int nv = gradreg ? 5 : 4;
-                finalize(part_a, nbm, nv, nv, slots, scales, out_dev);
-            }
-            inv2(Xf, work_buf(), X, P);
-            return;
-        }
         if (cols_sm_ok(p)) {
-            // column transform, Sherman-Morrison solve and inverse column transform of a
-            // (wf, cn) tile in LDS (fft.h fft_cols_sm): two passes over the spectrum instead of
-            // six.  The Xf buffer is left holding the column-inverse-transformed solution
-            // (xf_tiled: a reader of VAR_XF gets rfftn(X))
+            // the one-kernel column pass between the two row passes
             {
                 ProfScope ps(prof, PS_FFT_R2C);
                 fft_r2c<T>(st, planW, Y, U, (T)p.u_scale, Xf, H, P, (int64_t)W * P, P, (int64_t)Wf * P, P,
                            0, 0, 0, vf);
             }
-            if (!part_cs) SA_HIP(hipMalloc((void **)&part_cs, sizeof(double) * (int64_t)Wf * CN));
-            int64_t nt;
-            {
-                ProfScope ps(prof, PS_SM_SOLVE);
-                nt = fft_cols_sm<T>(st, planH, Xf, cv(SPORCO_AMD_VAR_DF), cv(SPORCO_AMD_VAR_SF), gram,
-                                    (T)p.rho, Wf, CN, K, W, obj, part_cs, sw.cols_sm_force_slab, &cols_sm_form);
-            }
-            if (obj) {
-                const int slots[1] = {SPORCO_AMD_OUT_DFID};
-                const double scales[1] = {1.0 / ((double)H * W)};
-                finalize(part_cs, (int)nt, 1, 1, slots, scales, out_dev);
-            }
-            xf_tiled = true;
+            run_cols_sm(p, obj, out_dev);
+            xf_tiled = true;       // (a reader of VAR_XF gets rfftn(X))
             {
                 ProfScope ps(prof, PS_FFT_C2R);
                 fft_c2r<T>(st, planW, Xf, X, H, P, (int64_t)Wf * P, P, (int64_t)W * P, P,
@@ -134,23 +136,13 @@
             }
             return;
         }
-        int nb;
+        // (ConvBPDNGradReg: the gradient term; AddMaskSim and ConvBPDNJoint differ in the y step only)
+        fwd2(Y, U, (T)p.u_scale, Xf, P, vf);
         GradTerm<T> gt;
         if (gradreg) gt = grad_term(p.mu);
-        {
-            ProfScope ps(prof, PS_SM_SOLVE);
-            nb = launch_sm_solve<T>(st, Xf, Xf, cv(SPORCO_AMD_VAR_DF), cv(SPORCO_AMD_VAR_SF), gram,
-                                    (T)p.rho, npix, CN, K, W, obj, xr, part_a,
-                                    gradreg ? &gt : nullptr);
-        }
-        if (obj || xr) {
-            const int slots[5] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_XRRS_D2,
-                                  SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2,
-                                  SPORCO_AMD_OUT_RGR};
-            const double scales[5] = {1.0 / ((double)H * W), 1.0, 1.0, 1.0, 1.0 / ((double)H * W)};
-            const int nv = gradreg ? 5 : 4;
-            finalize(part_a, nb, nv, nv, slots, scales, out_dev);
-        }
+        const int nb = generic_solve(Xf, Xf, cv(SPORCO_AMD_VAR_SF), (T)p.rho, obj, xr, gradreg ? &gt : nullptr,
+                                     gradreg ? p.mu : -1.0);
+        if (obj || xr) finalize_solve(nb, gradreg ? 5 : 4, 1.0 / ((double)H * W), SPORCO_AMD_OUT_RGR, out_dev);
         inv2(Xf, work_buf(), X, P);
     }
 
@@ -287,31 +279,12 @@
         T *const ybuf = gv_in ? static_cast<T *>(vars[SPORCO_AMD_VAR_Y]) : rv(SPORCO_AMD_VAR_Y);
         T *const ubuf = gv_in ? static_cast<T *>(vars[SPORCO_AMD_VAR_U]) : rv(SPORCO_AMD_VAR_U);
         xstep_impl(p, out_dev, gv_in ? ubuf : nullptr, it.cur.thr);
-        PostParams<T> pp;
-        pp.x = rv(SPORCO_AMD_VAR_X);
-        pp.y = ybuf;
-        pp.u = ubuf;
+        PostParams<T> pp = post_params(p, rv(SPORCO_AMD_VAR_X), ybuf, ubuf);
         pp.v_in = gv_in ? ubuf : nullptr;
         pp.v_out = gv_out ? ubuf : nullptr;
         pp.thr_prev = it.cur.thr;
+        if (p.flags & F_JOINT) pp.thr21 = (T)(p.mu / p.rho);
         commit_generic_v(p, gv_out);
-        pp.rlx = (T)p.rlx;
-        pp.thr = (T)(p.lmbda / p.rho);
-        pp.thr21 = (T)(p.mu / p.rho);
-        pp.u_scale = (T)p.u_scale;
-        pp.flags = p.flags;
-        pp.d = d5();
-        pp.dH = p.dH;
-        pp.dW = p.dW;
-        pp.wl1 = wl1;
-        pp.wl21 = wl21;
-        pp.ams = ams_of(p);
-        pp.ams_k = ams_k0();
-        pp.ams_n = ams_n();
-        const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                              SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1,
-                              SPORCO_AMD_OUT_L21};
-        const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
         {
             x_written();
             int nb;
@@ -319,7 +292,7 @@
                 ProfScope ps(prof, PS_ADMM_POST);
                 nb = launch_admm_post<T>(st, pp, part_b);
             }
-            finalize(part_b, nb, 8, 7, slots, scales, out_dev);
+            finalize_post(part_b, nb, 7, true, out_dev);
         }
         if ((p.flags & F_OBJ) && (p.flags & F_FEVAL_Y)) dfid_at(rv(SPORCO_AMD_VAR_Y), out_dev, &p);
         gen_epoch = touch_epoch;
@@ -343,19 +316,7 @@
                        0, 0, 0, &vfi);
         }
         t_ready = false;
-        const bool obj = (p.flags & F_OBJ) && !(p.flags & F_FEVAL_Y);
-        if (!part_cs) SA_HIP(hipMalloc((void **)&part_cs, sizeof(double) * (int64_t)Wf * CN));
-        int64_t nt;
-        {
-            ProfScope ps(prof, PS_SM_SOLVE);
-            nt = fft_cols_sm<T>(st, planH, Xf, cv(SPORCO_AMD_VAR_DF), cv(SPORCO_AMD_VAR_SF), gram, (T)p.rho, Wf, CN,
-                                K, W, obj, part_cs, sw.cols_sm_force_slab, &cols_sm_form);
-        }
-        if (obj) {
-            const int slots[1] = {SPORCO_AMD_OUT_DFID};
-            const double scales[1] = {1.0 / ((double)H * W)};
-            finalize(part_cs, (int)nt, 1, 1, slots, scales, out_dev);
-        }
+        run_cols_sm(p, (p.flags & F_OBJ) && !(p.flags & F_FEVAL_Y), out_dev);
         stable_run = p.u_scale == 1.0 ? stable_run + 1 : 0;
         const bool emit = stable_run >= 2 && !sw.no_speculation;
         if (emit && !gemit) big_alloc((void **)&gemit, var_alloc_bytes(SPORCO_AMD_VAR_XF));
@@ -368,30 +329,18 @@
             SA_HIP(hipMalloc((void **)&part_vpost, sizeof(double) * 8 * nblk));
             part_vpost_cap = nblk;
         }
-        PostParams<T> pp;
-        pp.x = nullptr;
-        pp.y = pp.u = nullptr;
+        // (gvform_ok: no weight array, no F_JOINT, no F_AMS on this path)
+        PostParams<T> pp = post_params(p, nullptr, nullptr, nullptr);
         pp.v_in = vbuf;
         pp.v_out = vbuf;
         pp.thr_prev = it.cur.thr;
-        pp.rlx = (T)p.rlx;
-        pp.thr = (T)(p.lmbda / p.rho);
-        pp.thr21 = T(0);
-        pp.u_scale = (T)p.u_scale;
-        pp.flags = p.flags;
-        pp.d = d5();
-        pp.dH = p.dH;
-        pp.dW = p.dW;
         int64_t nb;
         {
             ProfScope ps(prof, emit ? PS_C2R_VPOST_EMIT : PS_C2R_VPOST);
             nb = fft_c2r_vpost<T>(st, planW, Xf, H, P, (int64_t)Wf * P, P, T(1.0 / ((double)H * (double)W)), pp,
                                   emit ? gemit : nullptr, (int64_t)Wf * P, P, part_vpost);
         }
-        const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2, SPORCO_AMD_OUT_Y2,
-                              SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1, SPORCO_AMD_OUT_L21};
-        const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
-        finalize(part_vpost, (int)nb, 8, 7, slots, scales, out_dev);
+        finalize_post(part_vpost, (int)nb, 7, true, out_dev);
         commit_generic_v(p, true);
         // X of this iteration: one c2r row pass of the column pass's output away
         x_invalid = p.flags & F_NO_X;
@@ -443,11 +392,7 @@
                                       wl1, wl21, (p.flags & F_AMS) ? ams_k0() : -1, part_b,
                                       ams_n());
         }
-        const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                              SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1,
-                              SPORCO_AMD_OUT_L21};
-        const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
-        finalize(part_b, nb, 8, 7, slots, scales, out_dev);
+        finalize_post(part_b, nb, 7, true, out_dev);
         if ((p.flags & F_OBJ) && (p.flags & F_FEVAL_Y)) dfid_at(rv(SPORCO_AMD_VAR_Y), out_dev, &p);
     }
 
@@ -456,7 +401,8 @@
         launch_scale<T>(st, rv(SPORCO_AMD_VAR_U), (T)s, E);
     }
 
-    void reconstruct(int var, void *dst) override {
+    // irfftn(sum_k Df rfftn(var)) into sreal, copied out to the host or to device memory
+    void reconstruct_to(int var, void *dst, hipMemcpyKind kind) {
         require_ready();
         SA_REQUIRE(!var_is_complex(var), "reconstruct needs a real state variable");
         before_read(var);
@@ -467,24 +413,11 @@
             inner_df(wk);
         }
         inv2(innerb, innerb, sreal, CNs);
-        SA_HIP(hipMemcpyAsync(dst, sreal, sizeof(T) * (int64_t)H * W * CNs, hipMemcpyDeviceToHost, st));
+        SA_HIP(hipMemcpyAsync(dst, sreal, sizeof(T) * (int64_t)H * W * CNs, kind, st));
         sync();
     }
-    void reconstruct_dev(int var, void *dst_dev) override {
-        require_ready();
-        SA_REQUIRE(!var_is_complex(var), "reconstruct needs a real state variable");
-        before_read(var);
-        cx<T> *wk = work_buf();
-        fwd2(rv(var), nullptr, T(0), wk, P);
-        {
-            ProfScope ps(prof, PS_OTHER);
-            inner_df(wk);
-        }
-        inv2(innerb, innerb, sreal, CNs);
-        SA_HIP(hipMemcpyAsync(dst_dev, sreal, sizeof(T) * (int64_t)H * W * CNs,
-                              hipMemcpyDeviceToDevice, st));
-        sync();
-    }
+    void reconstruct(int var, void *dst) override { reconstruct_to(var, dst, hipMemcpyDeviceToHost); }
+    void reconstruct_dev(int var, void *dst_dev) override { reconstruct_to(var, dst_dev, hipMemcpyDeviceToDevice); }
 
     void dhs_absmax(double *out_host) override {
         require_ready();

@@ -49,34 +49,11 @@
         const bool obj = p.flags & F_OBJ, xr = p.flags & F_XRRS;
         const double mu_eff = p.mu / p.rho;
         const GradTerm<T> gt = grad_term(mu_eff);
-        int nb;
-        if (Cd > 1) {
-            if (!ism_gam) {
-                SA_HIP(hipMalloc((void **)&ism_gam, sizeof(cx<T>) * npix * Cd * K));
-                SA_HIP(hipMalloc((void **)&ism_del, sizeof(cx<T>) * npix * Cd));
-                SA_HIP(hipMalloc((void **)&ism_mm, sizeof(cx<T>) * npix * Cd * Cd));
-            }
-            ProfScope ps(prof, PS_SM_SOLVE);
-            // (the tables hold the diagonal: a change of rho moves mu / rho and rebuilds them)
-            if (!ism_valid || ism_rho != 1.0 || ism_mu != mu_eff) {
-                launch_ism_setup<T>(st, Df, ism_gam, ism_del, ism_mm, npix, Cd, K, T(1), &gt, W);
-                ism_valid = true;
-                ism_rho = 1.0;
-                ism_mu = mu_eff;
-            }
-            nb = launch_ism_solve<T>(st, Vf, Xf, Df, innerb, ism_gam, ism_del, ism_mm, T(1), npix, Cd, N, K, W, obj,
-                                     xr, part_a, &gt);
-        } else {
-            ProfScope ps(prof, PS_SM_SOLVE);
-            nb = launch_sm_solve<T>(st, Vf, Xf, Df, innerb, gram, T(1), npix, CN, K, W, obj, xr, part_a, &gt);
-        }
-        if (obj || xr) {
-            // (partial 0 is the solve's own residual against the block-0 spectrum: not a statistic here)
-            const int slots[5] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2,
-                                  SPORCO_AMD_OUT_XRRS_B2, SPORCO_AMD_OUT_RGRX};
-            const double scales[5] = {0.0, 1.0, 1.0, 1.0, 1.0 / ((double)H * W)};
-            finalize(part_a, nb, 5, 5, slots, scales, out_dev);
-        }
+        // (the tables of the multi-channel solve hold the diagonal: a change of rho moves mu / rho and
+        // rebuilds them; partial 0 is the solve's own residual against the block-0 spectrum: not a
+        // statistic here)
+        int nb = generic_solve(Vf, Xf, innerb, T(1), obj, xr, &gt, mu_eff);
+        if (obj || xr) finalize_solve(nb, 5, 0.0, SPORCO_AMD_OUT_RGRX, out_dev);
         inv2(Xf, work_buf(), X, P);
         // block 0: AXnr = D x
         {
@@ -86,32 +63,13 @@
         inv2(innerb, innerb, sreal, CNs);
         // block 1: relax, y1 = prox_l1 (+ NonNegCoef / NoBndryCross), u1, the sums, Yprev - Y
         T *dy1 = want_dual ? rv(SPORCO_AMD_VAR_AX) : nullptr;
-        PostParams<T> pp;
-        pp.x = X;
-        pp.y = Y1;
-        pp.u = U1;
-        pp.rlx = (T)p.rlx;
-        pp.thr = (T)(p.lmbda / p.rho);
-        pp.thr21 = T(0);
-        pp.u_scale = us;
-        pp.flags = p.flags;
-        pp.d = d5();
-        pp.dH = p.dH;
-        pp.dW = p.dW;
-        pp.wl1 = wl1;
-        pp.wl21 = wl21;
-        pp.ams_k = Ku - 1;
+        PostParams<T> pp = post_params(p, X, Y1, U1);
         pp.dy_out = dy1;
         {
             ProfScope ps(prof, PS_ADMM_POST);
             nb = launch_admm_post<T>(st, pp, part_b);
         }
-        {
-            const int slots[6] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                                  SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1};
-            const double scales[6] = {1, 0, 1, 1, 1, 1};
-            finalize(part_b, nb, 8, 6, slots, scales, out_dev);
-        }
+        finalize_post(part_b, nb, 6, false, out_dev);
         L1Y0Args<T> ya;
         ya.ax0nr = sreal;
         ya.y0 = Y0;

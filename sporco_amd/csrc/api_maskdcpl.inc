@@ -158,12 +158,7 @@
         x_written();
         md_x_pending = !(p.flags & F_KEEP_X);
         int nb;
-        {
-            const int slots[6] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                                  SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1};
-            const double scales[6] = {1, 0, 1, 1, 1, 1};
-            finalize(part_rows, (int)nt, 8, 6, slots, scales, out_dev);
-        }
+        finalize_post(part_rows, (int)nt, 6, false, out_dev);
         md_block0(p, out_dev, ball);
         if (p.flags & F_RESID) {
             fwd2(U0, nullptr, T(0), innerb, CNs);
@@ -215,6 +210,7 @@
         cx<T> *Xf = cv(SPORCO_AMD_VAR_XF), *Df = cv(SPORCO_AMD_VAR_DF);
         cx<T> *Vf = cv(SPORCO_AMD_VAR_VF), *Gf = cv(SPORCO_AMD_VAR_GF);
         // xstep: b = conj(Df) rfftn(y0 - u0 + s) + rfftn(y1 - u1); (D^H D + I) Xf = b
+        // (the block-0 spectrum in the signal's place; partial 0 is the solve's own residual against it)
         {
             ProfScope ps(prof, PS_OTHER);
             launch_md_pre<T>(st, Y0, U0, md_s, sreal, us, ns);
@@ -222,34 +218,8 @@
         fwd2(sreal, nullptr, T(0), innerb, CNs);
         fwd2(Y1, U1, us, Vf, P);
         const bool xr = p.flags & F_XRRS;
-        int nb;
-        if (Cd > 1) {
-            if (!ism_gam) {
-                SA_HIP(hipMalloc((void **)&ism_gam, sizeof(cx<T>) * npix * Cd * K));
-                SA_HIP(hipMalloc((void **)&ism_del, sizeof(cx<T>) * npix * Cd));
-                SA_HIP(hipMalloc((void **)&ism_mm, sizeof(cx<T>) * npix * Cd * Cd));
-            }
-            ProfScope ps(prof, PS_SM_SOLVE);
-            // (ism_mu: tables left by a gradient-regularised solve on this handle are not these)
-            if (!ism_valid || ism_rho != 1.0 || ism_mu != -1.0) {
-                launch_ism_setup<T>(st, Df, ism_gam, ism_del, ism_mm, npix, Cd, K, T(1));
-                ism_valid = true;
-                ism_rho = 1.0;
-                ism_mu = -1.0;
-            }
-            nb = launch_ism_solve<T>(st, Vf, Xf, Df, innerb, ism_gam, ism_del, ism_mm, T(1), npix, Cd,
-                                     N, K, W, false, xr, part_a);
-        } else {
-            ProfScope ps(prof, PS_SM_SOLVE);
-            nb = launch_sm_solve<T>(st, Vf, Xf, Df, innerb, gram, T(1), npix, CN, K, W, false, xr,
-                                    part_a);
-        }
-        if (xr) {
-            const int slots[4] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_XRRS_D2,
-                                  SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2};
-            const double scales[4] = {0.0, 1.0, 1.0, 1.0};
-            finalize(part_a, nb, 4, 4, slots, scales, out_dev);
-        }
+        int nb = generic_solve(Vf, Xf, innerb, T(1), false, xr, nullptr, -1.0);
+        if (xr) finalize_solve(nb, 4, 0.0, SPORCO_AMD_OUT_RGR, out_dev);
         inv2(Xf, work_buf(), X, P);
         // block 0: AXnr = D x, relax, y0, u0
         {
@@ -258,31 +228,12 @@
         }
         inv2(innerb, innerb, sreal, CNs);
         // block 1: relax, y1 = prox_l1 (+ NonNegCoef / NoBndryCross), u1 and the sums
-        PostParams<T> pp;
-        pp.x = X;
-        pp.y = Y1;
-        pp.u = U1;
-        pp.rlx = (T)p.rlx;
-        pp.thr = (T)(p.lmbda / p.rho);
-        pp.thr21 = T(0);
-        pp.u_scale = us;
-        pp.flags = p.flags;
-        pp.d = d5();
-        pp.dH = p.dH;
-        pp.dW = p.dW;
-        pp.wl1 = wl1;
-        pp.wl21 = wl21;
-        pp.ams_k = Ku - 1;
+        const PostParams<T> pp = post_params(p, X, Y1, U1);
         {
             ProfScope ps(prof, PS_ADMM_POST);
             nb = launch_admm_post<T>(st, pp, part_b);
         }
-        {
-            const int slots[6] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                                  SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1};
-            const double scales[6] = {1, 0, 1, 1, 1, 1};
-            finalize(part_b, nb, 8, 6, slots, scales, out_dev);
-        }
+        finalize_post(part_b, nb, 6, false, out_dev);
         md_block0(p, out_dev, ball);
         if (p.flags & F_RESID) {
             // dual residual (cbpdn.py:1814-1818): A^T u = irfftn(conj(Df) rfftn(u0)) + u1, its

@@ -99,12 +99,7 @@
             nb = launch_pd_solve<T>(st, a, &wave);
         }
         ++(wave ? pd_wave_launches : pd_generic_launches);
-        if (a.want_obj || a.want_xrrs) {
-            const int slots[4] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2,
-                                  SPORCO_AMD_OUT_XRRS_B2};
-            const double scales[4] = {1.0 / ((double)H * W), 1.0, 1.0, 1.0};
-            finalize(part_a, nb, 4, 4, slots, scales, out_dev);
-        }
+        if (a.want_obj || a.want_xrrs) finalize_solve(nb, 4, 1.0 / ((double)H * W), SPORCO_AMD_OUT_RGR, out_dev);
         inv2(Xf, zf, rv(SPORCO_AMD_VAR_X), P);
     }
 

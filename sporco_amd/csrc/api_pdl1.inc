@@ -119,31 +119,19 @@
         inv2(Xf, work_buf(), X, P);
         inv2(pl_ax0f, pl_ax0f, pl_ax0, csn);
         // block 1: relax, y1 = prox (+ NonNegCoef / NoBndryCross), u1, the sums
-        PostParams<T> pp;
-        pp.x = X;
-        pp.y = Y1;
-        pp.u = U1;
-        pp.rlx = (T)p.rlx;
-        pp.thr = joint ? T(0) : (T)(p.lmbda / p.rho);
-        pp.thr21 = joint ? (T)(p.lmbda / p.rho) : T(0);
-        pp.u_scale = us;
-        pp.flags = p.flags;
-        pp.d = d5();
-        pp.dH = p.dH;
-        pp.dW = p.dW;
-        pp.wl1 = joint ? Weight<T>() : wl1;
+        // (joint: lmbda / rho is the l2,1 threshold, the l1 threshold zero and L1Weight ignored; the
+        // handle's l2,1 weight array is never this class's)
+        PostParams<T> pp = post_params(p, X, Y1, U1);
+        if (joint) {
+            std::swap(pp.thr, pp.thr21);
+            pp.wl1 = Weight<T>();
+        }
         pp.wl21 = Weight<T>();
-        pp.ams_k = Ku - 1;
         {
             ProfScope ps(prof, PS_ADMM_POST);
             nb = launch_admm_post<T>(st, pp, part_b);
         }
-        {
-            const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2, SPORCO_AMD_OUT_Y2,
-                                  SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1, SPORCO_AMD_OUT_L21};
-            const double scales[7] = {1, 0, 1, 1, 1, 1, 1};
-            finalize(part_b, nb, 8, joint ? 7 : 6, slots, scales, out_dev);
-        }
+        finalize_post(part_b, nb, joint ? 7 : 6, false, out_dev);
         // block 0
         L1Y0Args<T> ya;
         ya.ax0nr = pl_ax0;

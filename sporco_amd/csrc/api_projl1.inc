@@ -47,10 +47,7 @@
             ProfScope ps(prof, PS_PROJL1_APPLY);
             nb = launch_projl1_apply<T>(st, a, g, part_b);
         }
-        const int slots[5] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2, SPORCO_AMD_OUT_Y2,
-                              SPORCO_AMD_OUT_U2};
-        const double scales[5] = {1, 1, 1, 1, 1};
-        finalize(part_b, nb, 8, 5, slots, scales, out_dev);
+        finalize_post(part_b, nb, 5, true, out_dev);
         const double *cnt = projl1_counter(pl_ws[0], g);
         SA_HIP(hipMemcpyAsync(out_dev + SPORCO_AMD_OUT_CGIT, cnt, sizeof(double), hipMemcpyDeviceToDevice, st));
         SA_HIP(hipMemcpyAsync(out_dev + SPORCO_AMD_OUT_CGN, cnt + 1, sizeof(double), hipMemcpyDeviceToDevice, st));

@@ -99,12 +99,7 @@
             ProfScope ps(prof, PS_RTV_SOLVE);
             nb = launch_rtv_solve<T>(st, a);
         }
-        if (a.want_obj || a.want_xrrs) {
-            const int slots[4] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2,
-                                  SPORCO_AMD_OUT_XRRS_B2};
-            const double scales[4] = {1.0 / ((double)H * W), 1.0, 1.0, 1.0};
-            finalize(part_a, nb, 4, 4, slots, scales, out_dev);
-        }
+        if (a.want_obj || a.want_xrrs) finalize_solve(nb, 4, 1.0 / ((double)H * W), SPORCO_AMD_OUT_RGR, out_dev);
         inv2(Xf, work_buf(), rv(SPORCO_AMD_VAR_X), P);
         inv2(rtv_rwf, rtv_rwf, rtv_rw, CN);
     }

@@ -65,14 +65,33 @@
         launch_finalize(st, part, nblocks, stride, nvals, slots, scales, is_max, out_dev);
     }
 
+    // ---- the sum tables of the ADMM iterations ------------------------------------------------
+    // An epilogue (launch_admm_post, the row epilogues, admm_stats) leaves rows of 8 partials; their
+    // first nvals columns go to these slots.  with_s2 false: the dual residual is summed elsewhere
+    // (the two-block classes) and S2 stays at zero.
+    static constexpr int kPostSlots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
+                                          SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1,
+                                          SPORCO_AMD_OUT_L21};
+    static constexpr double kPostScales[2][7] = {{1, 0, 1, 1, 1, 1, 1}, {1, 1, 1, 1, 1, 1, 1}};
+    void finalize_post(const double *part, int nb, int nvals, bool with_s2, double *out_dev) {
+        finalize(part, nb, 8, nvals, kPostSlots, kPostScales[with_s2 ? 1 : 0], out_dev);
+    }
+    // A solve leaves rows of nvals partials in part_a: the data fidelity (dfid_scale 0: the solve
+    // ran against a block-0 spectrum and its residual is no statistic), the LinSolveCheck triple
+    // and, nvals = 5, the gradient term, which goes to grad_slot (OUT_RGR or OUT_RGRX)
+    void finalize_solve(int nb, int nvals, double dfid_scale, int grad_slot, double *out_dev) {
+        const int slots[5] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2,
+                              SPORCO_AMD_OUT_XRRS_B2, grad_slot};
+        const double scales[5] = {dfid_scale, 1.0, 1.0, 1.0, 1.0 / ((double)H * W)};
+        finalize(part_a, nb, nvals, nvals, slots, scales, out_dev);
+    }
+
     // the sums of a three-launch iteration in one launch over both partial arrays: the six (joint:
     // seven) of the `nt` row tiles of the epilogue, and the column kernel's data-fidelity (and
     // gradient) term
     void finalize_iter_sums(const sporco_amd_admm_params &p, int64_t nt, double *out_dev) {
-        const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_AX2,
-                              SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_L1,
-                              SPORCO_AMD_OUT_L21};
-        const double scales[7] = {1, 1, 1, 1, 1, 1, 1};
+        const int *slots = kPostSlots;
+        const double *scales = kPostScales[1];
         const int nrow = (p.flags & F_JOINT) ? 7 : 6;
         const int fslots[2] = {SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_RGR};
         const double fscales[2] = {1.0 / ((double)H * W), 1.0 / ((double)H * W)};
@@ -199,6 +218,29 @@
         ra.P = P;
         ra.partials = part_rows;
         return ra;
+    }
+    // the streaming epilogue (launch_admm_post, fft_c2r_vpost) on the (Y, U) form of x, y, u with the
+    // plain l1 threshold: the call site adds the routing of a single-array iterate (v_in / v_out /
+    // thr_prev), thr21 under F_JOINT and dy_out.  The AddMaskSim fields are read under F_AMS only.
+    PostParams<T> post_params(const sporco_amd_admm_params &p, const T *x, T *y, T *u) {
+        PostParams<T> pp;
+        pp.x = x;
+        pp.y = y;
+        pp.u = u;
+        pp.rlx = (T)p.rlx;
+        pp.thr = (T)(p.lmbda / p.rho);
+        pp.thr21 = T(0);
+        pp.u_scale = (T)p.u_scale;
+        pp.flags = p.flags;
+        pp.d = d5();
+        pp.dH = p.dH;
+        pp.dW = p.dW;
+        pp.wl1 = wl1;
+        pp.wl21 = wl21;
+        pp.ams = ams_of(p);
+        pp.ams_k = ams_k0();
+        pp.ams_n = ams_n();
+        return pp;
     }
 
     // ---- tile-major operands of the fused X-step -----------------------------------
