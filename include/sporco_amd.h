@@ -1055,6 +1055,61 @@ int sporco_amd_proj_l1(int dtype, int64_t outer, int64_t P, int64_t inner, const
 /* rfl2norm2 (sporco/fft.py:449-484) of complex xf (H,W/2+1,P) for spatial (H,W). */
 int sporco_amd_rfl2norm2(int dtype, int32_t H, int32_t W, int64_t P, const void *xf,
                          double *out);
+/* out = x * y, elementwise, on real device arrays of n elements (DeviceArray * DeviceArray). */
+int sporco_amd_dev_mul(int dtype, int64_t n, const void *x, const void *y, void *out);
+
+/* ---- l2-TV denoising: sporco.admm.tvl2.TVL2Denoise (sporco/admm/tvl2.py:27-372) ----------------
+ * minimise (1/2) ||Wdf (x - s)||^2 + lmbda ||Wtv sqrt((G_0 x)^2 + (G_1 x)^2)||_1 by ADMM on
+ * (G_0; G_1) x = (y_0; y_1), G_i the forward difference along axis i with a zero last row.  Every step
+ * is a nearest-neighbour stencil (csrc/csc_tvd.h); the handle is a small one of its own: the arrays of
+ * one (H, W, P) problem, P the product of the trailing axes, and a stream -- no dictionary, no
+ * transforms.  vector_tv: the l2 norm of the y step also runs over the first of the trailing axes
+ * (C channels, P = C N, C <= 8; the reference's caxis=2), else every plane is a problem of its own.
+ * X starts at S (set by uploading S); Y, U start at zero. */
+typedef struct sporco_amd_tvd *sporco_amd_tvd_t;
+#define SPORCO_AMD_TVD_S 0    /* real (H,W,P)    the signal; uploading it also sets X = S          */
+#define SPORCO_AMD_TVD_X 1    /* real (H,W,P)    the iterate of the x step                         */
+#define SPORCO_AMD_TVD_Y 2    /* real (2,H,W,P)  the blocks (y_0, y_1) of Y                        */
+#define SPORCO_AMD_TVD_U 3    /* real (2,H,W,P)  ... and of U (without a pending u_scale)          */
+#define SPORCO_AMD_TVD_WDF 4  /* real (H,W,P)    DFidWeight array (upload NULL: the scalar wdf)    */
+#define SPORCO_AMD_TVD_WTV 5  /* real (H,W,P)    TVWeight array (upload NULL: the scalar wtv;      */
+                              /*                 not with vector_tv)                               */
+typedef struct {
+    double rho, lmbda, rlx;
+    double u_scale;   /* pending U /= rsf (admm.py:573): the sweeps and the y step apply it          */
+    double wdf, wtv;  /* scalar weights, read where no array is set                                   */
+    int32_t geval_y;  /* RegTV at Y (else at A X)                                                     */
+} sporco_amd_tvd_params;
+int sporco_amd_tvd_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv,
+                          int device, void *stream, sporco_amd_tvd_t *out);
+int sporco_amd_tvd_destroy(sporco_amd_tvd_t h);
+int sporco_amd_tvd_sync(sporco_amd_tvd_t h);
+/* The launch plan: out = (V, items per row, strips, rows per segment, segments, columns a strip covers);
+ * V is the elements of an item (the access width; the channel count with vector_tv). */
+int sporco_amd_tvd_plan(sporco_amd_tvd_t h, int64_t out[6]);
+/* Copy an array in or out; on_device: src / dst is a device pointer (no host traffic).  After Y, U or X
+ * have been written, sporco_amd_tvd_adjoint must run before the next sweep. */
+int sporco_amd_tvd_upload(sporco_amd_tvd_t h, int var, const void *src, int on_device);
+int sporco_amd_tvd_download(sporco_amd_tvd_t h, int var, void *dst, int on_device);
+/* n Jacobi sweeps of the x step (tvl2.py:362-371) on P = A^T (Y - u_scale U). */
+int sporco_amd_tvd_sweeps(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p, int32_t n);
+/* The norms of linalg.rrs(rho A^T A X + Wdf^2 X, Wdf^2 S + rho P) at the current X (tvl2.py:248-251):
+ * out[OUT_XRRS_D2], out[OUT_XRRS_AX2], out[OUT_XRRS_B2]; one launch and one host read (GSTol > 0). */
+int sporco_amd_tvd_gsres(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p,
+                         double out[SPORCO_AMD_OUT_COUNT]);
+/* relax_AX + ystep + ustep in one launch, then A^T of the new Y, U and of Y - Yprev in a second, and one
+ * host read.  out: OUT_R2, OUT_AX2, OUT_Y2 as for admm_iter; OUT_S2 = ||A^T (Y - Yprev)||^2 and
+ * OUT_U2 = ||A^T U||^2 (rho applied by the host); OUT_DFID = ||Wdf (X - S)||^2 (not halved);
+ * OUT_L21 = sum Wtv sqrt(sum g^2), g = Y with geval_y, else A X; OUT_XRRS_* as for tvd_gsres.
+ * U is stored with u_scale applied: the caller's pending factor is 1 afterwards. */
+int sporco_amd_tvd_ystep(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p,
+                         double out[SPORCO_AMD_OUT_COUNT]);
+/* A^T (Y - U) and A^T U of the current arrays (after an upload of Y, U). */
+int sporco_amd_tvd_adjoint(sporco_amd_tvd_t h);
+/* Per-kernel event timing of the handle's launches, as sporco_amd_csc_profile / _profile_read. */
+int sporco_amd_tvd_profile(sporco_amd_tvd_t h, int enable);
+int sporco_amd_tvd_profile_read(sporco_amd_tvd_t h, int slot, const char **name, double *total_ms,
+                                int64_t *count);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,10 @@ EXPORTS = (
     'sporco_amd_rfftn2', 'sporco_amd_irfftn2', 'sporco_amd_solvedbi_sm',
     'sporco_amd_inner', 'sporco_amd_prox_l1', 'sporco_amd_prox_l1w', 'sporco_amd_prox_sl1l2',
     'sporco_amd_proj_l2', 'sporco_amd_proj_l1', 'sporco_amd_rfl2norm2',
+    'sporco_amd_dev_mul',
+    'sporco_amd_tvd_create', 'sporco_amd_tvd_destroy', 'sporco_amd_tvd_sync', 'sporco_amd_tvd_plan',
+    'sporco_amd_tvd_upload', 'sporco_amd_tvd_download', 'sporco_amd_tvd_sweeps', 'sporco_amd_tvd_gsres',
+    'sporco_amd_tvd_ystep', 'sporco_amd_tvd_adjoint', 'sporco_amd_tvd_profile', 'sporco_amd_tvd_profile_read',
 )
 
 
@@ -160,6 +164,15 @@ class InhibParams(ctypes.Structure):
     _fields_ = [('lmbda', ctypes.c_double), ('mu', ctypes.c_double), ('gamma', ctypes.c_double),
                 ('smooth', ctypes.c_double), ('flags', ctypes.c_uint32)]
 
+
+class TvdParams(ctypes.Structure):
+    """sporco_amd_tvd_params: scalars of one TVL2Denoise launch group."""
+    _fields_ = [('rho', ctypes.c_double), ('lmbda', ctypes.c_double), ('rlx', ctypes.c_double),
+                ('u_scale', ctypes.c_double), ('wdf', ctypes.c_double), ('wtv', ctypes.c_double),
+                ('geval_y', ctypes.c_int32)]
+
+
+TVD_S, TVD_X, TVD_Y, TVD_U, TVD_WDF, TVD_WTV = range(6)
 
 REDUCE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
 EUNSUPPORTED = -5
@@ -364,6 +377,19 @@ def load(path=None):
         'sporco_amd_proj_l2': [ctypes.c_int, i64, i64, i64, vp, dbl, vp],
         'sporco_amd_proj_l1': [ctypes.c_int, i64, i64, i64, vp, dbl, vp],
         'sporco_amd_rfl2norm2': [ctypes.c_int, i32, i32, i64, vp, dptr],
+        'sporco_amd_dev_mul': [ctypes.c_int, i64, vp, vp, vp],
+        'sporco_amd_tvd_create': [ctypes.c_int, i32, i32, i64, i32, i32, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_tvd_destroy': [vp], 'sporco_amd_tvd_sync': [vp],
+        'sporco_amd_tvd_plan': [vp, ctypes.POINTER(i64)],
+        'sporco_amd_tvd_upload': [vp, ctypes.c_int, vp, ctypes.c_int],
+        'sporco_amd_tvd_download': [vp, ctypes.c_int, vp, ctypes.c_int],
+        'sporco_amd_tvd_sweeps': [vp, ctypes.POINTER(TvdParams), i32],
+        'sporco_amd_tvd_gsres': [vp, ctypes.POINTER(TvdParams), dptr],
+        'sporco_amd_tvd_ystep': [vp, ctypes.POINTER(TvdParams), dptr],
+        'sporco_amd_tvd_adjoint': [vp],
+        'sporco_amd_tvd_profile': [vp, ctypes.c_int],
+        'sporco_amd_tvd_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
+                                        ctypes.POINTER(i64)],
     }
     for name, argtypes in sig.items():
         getattr(lib, name).argtypes = argtypes
@@ -1105,4 +1131,97 @@ class Solver(object):
             check(self._lib.sporco_amd_csc_profile_read(self._h, slot, ctypes.byref(name),
                                                         ctypes.byref(ms), ctypes.byref(cnt)))
             res[name.value.decode()] = (ms.value, cnt.value)
+        return res
+
+
+class TvdHandle(object):
+    """Owner of one device-side TVL2Denoise problem (sporco_amd_tvd_*): arrays of shape
+    (H, W, P); ``vector_tv``: the l2 norm of the y step also runs over the first of the trailing axes
+    (``C`` channels)."""
+
+    def __init__(self, H, W, P, dtype, C=1, vector_tv=False, device=0, stream=None):
+        self.dims = (int(H), int(W), int(P))
+        self.dtype = np.dtype(dtype)
+        h = ctypes.c_void_p()
+        check(lib().sporco_amd_tvd_create(dtype_code(dtype), int(H), int(W), int(P), int(C),
+                                          1 if vector_tv else 0, int(device), ctypes.c_void_p(stream or 0),
+                                          ctypes.byref(h)))
+        self._h = h
+        self._lib = lib()
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sporco_amd_tvd_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        check(self._lib.sporco_amd_tvd_sync(self._h))
+
+    def plan(self):
+        """``dict(V, items, strips, R, nseg, TW)``: elements per item, items per row, strips per row,
+        rows per segment, segments, columns a strip covers."""
+        out = (ctypes.c_int64 * 6)()
+        check(self._lib.sporco_amd_tvd_plan(self._h, out))
+        return dict(zip(('V', 'items', 'strips', 'R', 'nseg', 'TW'), (int(v) for v in out)))
+
+    def var_shape(self, var):
+        return ((2,) if var in (TVD_Y, TVD_U) else ()) + self.dims
+
+    def upload(self, var, a):
+        """``a``: a host array, a device pointer (int) of an array of the variable's size, or None
+        (a weight goes back to its scalar)."""
+        if a is None:
+            check(self._lib.sporco_amd_tvd_upload(self._h, int(var), None, 0))
+        elif isinstance(a, int):
+            check(self._lib.sporco_amd_tvd_upload(self._h, int(var), ctypes.c_void_p(a), 1))
+        else:
+            a = _carr(a, self.dtype)
+            if a.size != int(np.prod(self.var_shape(var))):
+                raise ValueError("array of %d elements for a variable of shape %s" % (a.size, self.var_shape(var)))
+            check(self._lib.sporco_amd_tvd_upload(self._h, int(var), _ptr(a), 0))
+
+    def download(self, var, dst_ptr=None):
+        """To a new host array, or (``dst_ptr``: device pointer) device to device."""
+        if dst_ptr is not None:
+            check(self._lib.sporco_amd_tvd_download(self._h, int(var), ctypes.c_void_p(dst_ptr), 1))
+            return None
+        out = np.empty(self.var_shape(var), dtype=self.dtype)
+        check(self._lib.sporco_amd_tvd_download(self._h, int(var), _ptr(out), 0))
+        return out
+
+    def sweeps(self, params, n):
+        check(self._lib.sporco_amd_tvd_sweeps(self._h, ctypes.byref(params), int(n)))
+
+    def _sums(self, fn, params):
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(fn(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def gsres(self, params):
+        return self._sums(self._lib.sporco_amd_tvd_gsres, params)
+
+    def ystep(self, params):
+        return self._sums(self._lib.sporco_amd_tvd_ystep, params)
+
+    def adjoint(self):
+        check(self._lib.sporco_amd_tvd_adjoint(self._h))
+
+    def profile(self, enable):
+        check(self._lib.sporco_amd_tvd_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self):
+        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
+        res = {}
+        for slot in range(self._lib.sporco_amd_profile_slots()):
+            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
+            check(self._lib.sporco_amd_tvd_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
+                                                        ctypes.byref(cnt)))
+            if cnt.value:
+                res[name.value.decode()] = (ms.value, cnt.value)
         return res

@@ -1,3 +1,3 @@
 """Solver classes mirroring the reference sub-package of the same name."""
 
-__all__ = ['admm', 'cbpdn', 'cbpdn_cplx', 'cbpdnin', 'cbpdntv', 'ccmod', 'ccmodmd', 'pdcsc']
+__all__ = ['admm', 'cbpdn', 'cbpdn_cplx', 'cbpdnin', 'cbpdntv', 'ccmod', 'ccmodmd', 'pdcsc', 'tvl2']

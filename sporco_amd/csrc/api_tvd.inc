@@ -1,0 +1,186 @@
+// api_tvd.inc -- the handle of TVL2Denoise (sporco/admm/tvl2.py:27-372; kernels: csc_tvd.h).  Unlike the
+// other api_*.inc files this one is included by csc_api.hip at namespace scope, BELOW template Csc<T>:
+// the class has no dictionary and no transform and does not share a CSC solver's state.
+template <typename T> struct Tvd : TvdBase {
+    int device;
+    hipStream_t st = nullptr;
+    bool own_stream = false;
+    TvdPlan pl;
+    int64_t E;                      // H W P
+    T *s = nullptr, *x[2] = {nullptr, nullptr}, *y = nullptr, *u = nullptr, *dy = nullptr, *pd = nullptr, *q = nullptr;
+    T *wdf = nullptr, *wtv = nullptr;
+    bool have_wdf = false, have_wtv = false;
+    int cur = 0;                    // x[cur] is X
+    double *part_a = nullptr, *part_b = nullptr, *out_dev = nullptr, *out_pinned = nullptr;
+
+    Tvd(int H, int W, int64_t P, int C, bool vtv, int dev, void *stream) : device(dev) {
+        SA_HIP(hipSetDevice(device));
+        pl = tvd_plan(sizeof(T), H, W, P, C, vtv);
+        E = pl.L * H;
+        if (stream) {
+            st = (hipStream_t)stream;
+        } else {
+            SA_HIP(hipStreamCreate(&st));
+            own_stream = true;
+        }
+        prof.st = st;
+        for (T **p : {&s, &x[0], &x[1], &pd, &q}) alloc_zero(p, E);
+        for (T **p : {&y, &u, &dy}) alloc_zero(p, 2 * E);
+        SA_HIP(hipMalloc((void **)&part_a, sizeof(double) * kTvdSums * pl.blocks()));
+        SA_HIP(hipMalloc((void **)&part_b, sizeof(double) * kTvdSums * pl.blocks()));
+        SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
+        SA_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOutSlots, st));
+        SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
+    }
+    void alloc_zero(T **p, int64_t n) {
+        SA_HIP(hipMalloc((void **)p, sizeof(T) * n));
+        SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * n, st));
+    }
+    ~Tvd() override {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(st);
+        for (void *p : {(void *)s, (void *)x[0], (void *)x[1], (void *)y, (void *)u, (void *)dy, (void *)pd, (void *)q,
+                        (void *)wdf, (void *)wtv, (void *)part_a, (void *)part_b, (void *)out_dev})
+            if (p) (void)hipFree(p);
+        if (out_pinned) (void)hipHostFree(out_pinned);
+        if (own_stream) (void)hipStreamDestroy(st);
+    }
+
+    void sync() override { SA_HIP(hipStreamSynchronize(st)); }
+    void plan(int64_t out[6]) override {
+        out[0] = pl.cnt;
+        out[1] = pl.items;
+        out[2] = pl.strips;
+        out[3] = pl.rows;
+        out[4] = pl.nseg;
+        // the columns a strip of 256 items covers (at least one)
+        const int64_t per = pl.vtv ? pl.N : pl.P;
+        out[5] = std::max<int64_t>(1, (int64_t)kTvdThreads * (pl.vtv ? 1 : pl.cnt) / per);
+    }
+
+    T *var_buf(int var, int64_t *n) {
+        *n = (var == SPORCO_AMD_TVD_Y || var == SPORCO_AMD_TVD_U) ? 2 * E : E;
+        switch (var) {
+        case SPORCO_AMD_TVD_S: return s;
+        case SPORCO_AMD_TVD_X: return x[cur];
+        case SPORCO_AMD_TVD_Y: return y;
+        case SPORCO_AMD_TVD_U: return u;
+        case SPORCO_AMD_TVD_WDF: return wdf;
+        case SPORCO_AMD_TVD_WTV: return wtv;
+        default: throw Error(SPORCO_AMD_EINVAL, "tvd: unknown array id");
+        }
+    }
+    void upload(int var, const void *src, bool on_device) override {
+        if (var == SPORCO_AMD_TVD_WDF || var == SPORCO_AMD_TVD_WTV) {
+            bool &have = var == SPORCO_AMD_TVD_WDF ? have_wdf : have_wtv;
+            T *&w = var == SPORCO_AMD_TVD_WDF ? wdf : wtv;
+            have = src != nullptr;
+            if (!have) return;
+            SA_REQUIRE(var == SPORCO_AMD_TVD_WDF || !pl.vtv, "tvd: vector TV takes a scalar TVWeight");
+            if (!w) SA_HIP(hipMalloc((void **)&w, sizeof(T) * E));
+        }
+        SA_REQUIRE(src != nullptr, "tvd: null source");
+        int64_t n;
+        T *dst = var_buf(var, &n);
+        SA_HIP(hipMemcpyAsync(dst, src, sizeof(T) * n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        if (var == SPORCO_AMD_TVD_S)
+            SA_HIP(hipMemcpyAsync(x[cur], s, sizeof(T) * n, hipMemcpyDeviceToDevice, st));
+        sync();      // (the source may be pageable host memory, or a device array the caller frees next)
+    }
+    void download(int var, void *dst, bool on_device) override {
+        SA_REQUIRE(dst != nullptr, "tvd: null destination");
+        int64_t n;
+        const T *src = var_buf(var, &n);
+        SA_REQUIRE(src != nullptr, "tvd: this weight is a scalar");
+        SA_HIP(hipMemcpyAsync(dst, src, sizeof(T) * n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        sync();
+    }
+
+    TvdArgs<T> args(const sporco_amd_tvd_params &p) {
+        SA_REQUIRE(p.rho > 0.0, "rho must be positive");
+        TvdArgs<T> a;
+        a.s = s;
+        a.xin = x[cur];
+        a.xout = x[cur ^ 1];
+        a.y = y;
+        a.u = u;
+        a.dy = dy;
+        a.pd = pd;
+        a.q = q;
+        a.wdf = have_wdf ? wdf : nullptr;
+        a.wtv = have_wtv ? wtv : nullptr;
+        a.wdf_s = (T)p.wdf;
+        a.wtv_s = (T)p.wtv;
+        a.rho = (T)p.rho;
+        a.thr = (T)((T)p.lmbda / (T)p.rho);
+        a.rlx = (T)p.rlx;
+        a.u_scale = (T)p.u_scale;
+        a.geval_y = p.geval_y;
+        return a;
+    }
+    void read_out(double *out_host) {
+        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
+        sync();
+        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
+    }
+
+    void sweeps(const sporco_amd_tvd_params &p, int n) override {
+        for (int i = 0; i < n; ++i) {
+            ProfScope ps(prof, PS_TVD_SWEEP);
+            launch_tvd_sweep<T>(st, args(p), pl);
+            cur ^= 1;
+        }
+    }
+    void gsres(const sporco_amd_tvd_params &p, double *out_host) override {
+        TvdArgs<T> a = args(p);
+        a.partials = part_a;
+        {
+            ProfScope ps(prof, PS_TVD_YSTEP);
+            launch_tvd_ystep<T>(st, a, pl, true);
+        }
+        const int slots[3] = {SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2};
+        const double scales[3] = {1, 1, 1};
+        {
+            ProfScope ps(prof, PS_FINALIZE);
+            launch_finalize(st, part_a + 5, (int)pl.blocks(), kTvdSums, 3, slots, scales, false, out_dev);
+        }
+        read_out(out_host);
+    }
+    void ystep(const sporco_amd_tvd_params &p, double *out_host) override {
+        TvdArgs<T> a = args(p);
+        a.partials = part_a;
+        {
+            ProfScope ps(prof, PS_TVD_YSTEP);
+            launch_tvd_ystep<T>(st, a, pl, false);
+        }
+        a.partials = part_b;
+        {
+            ProfScope ps(prof, PS_TVD_ADJOINT);
+            launch_tvd_adjoint<T>(st, a, pl);
+        }
+        const int slots_a[8] = {SPORCO_AMD_OUT_R2,  SPORCO_AMD_OUT_AX2,     SPORCO_AMD_OUT_Y2,       SPORCO_AMD_OUT_DFID,
+                                SPORCO_AMD_OUT_L21, SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2};
+        const int slots_b[2] = {SPORCO_AMD_OUT_S2, SPORCO_AMD_OUT_U2};
+        const double ones[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+        {
+            ProfScope ps(prof, PS_FINALIZE);
+            launch_finalize2(st, part_a, (int)pl.blocks(), kTvdSums, 8, slots_a, ones, part_b, (int)pl.blocks(), kTvdSums,
+                             2, slots_b, ones, out_dev);
+        }
+        read_out(out_host);
+    }
+    void adjoint() override {
+        sporco_amd_tvd_params p = {1.0, 0.0, 1.0, 1.0, 1.0, 1.0, 1};
+        TvdArgs<T> a = args(p);
+        a.partials = part_b;
+        // (dY is whatever the last y step left, or zero: its sum is not read)
+        ProfScope ps(prof, PS_TVD_ADJOINT);
+        launch_tvd_adjoint<T>(st, a, pl);
+    }
+};
+
+TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, int device, void *stream) {
+    if (dtype == SPORCO_AMD_F32) return new Tvd<float>(H, W, P, C, vector_tv, device, stream);
+    if (dtype == SPORCO_AMD_F64) return new Tvd<double>(H, W, P, C, vector_tv, device, stream);
+    throw Error(SPORCO_AMD_EINVAL, "dtype must be SPORCO_AMD_F32 or SPORCO_AMD_F64");
+}

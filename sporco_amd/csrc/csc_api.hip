@@ -33,7 +33,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "ball_norms",       "ball_y0step",
                                     "pdl1_solve",       "pdl1_dual",
                                     "projl1_search",    "projl1_apply",
-                                    "projl1_pass0",     "projl1_cnstr"};
+                                    "projl1_pass0",     "projl1_cnstr",
+                                    "tvd_sweep",        "tvd_ystep",        "tvd_adjoint"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -646,6 +647,8 @@ template <typename T> struct Csc : CscBase {
 #include "api_pdl1.inc"
 #include "api_projl1.inc"
 };
+
+#include "api_tvd.inc"
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {
     if (dims.dtype == SPORCO_AMD_F32) return new Csc<float>(dims, device, stream, dict_channels, depth);

@@ -26,6 +26,7 @@
 #include "csc_rows.h"
 #include "csc_rtv.h"
 #include "csc_tv.h"
+#include "csc_tvd.h"
 #include "fft.h"
 
 #include <atomic>
@@ -110,6 +111,9 @@ enum ProfSlot {
     PS_PROJL1_APPLY,            // ... relax + shrink + u step
     PS_PROJL1_PASS0,            // ... the first search pass of the y step alone: every image, whole arrays
     PS_PROJL1_CNSTR,            // ... the constraint measure's read pass
+    PS_TVD_SWEEP,               // TVL2Denoise: one Jacobi sweep of the x step (csc_tvd.h)
+    PS_TVD_YSTEP,               // ... relax + y step + u step + the sums that need X
+    PS_TVD_ADJOINT,             // ... A^T (Y - U), A^T U and the dual-residual sums
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -306,6 +310,21 @@ static bool var_is_valid(int var) {
            (var >= SPORCO_AMD_VAR_DX && var < SPORCO_AMD_VAR_COUNT);
 }
 
+// The handle of TVL2Denoise (api_tvd.inc): the arrays of one (H, W, P) problem and a stream.
+struct TvdBase {
+    virtual ~TvdBase() {}
+    virtual void sync() = 0;
+    virtual void plan(int64_t out[6]) = 0;
+    virtual void upload(int var, const void *src, bool on_device) = 0;
+    virtual void download(int var, void *dst, bool on_device) = 0;
+    virtual void sweeps(const sporco_amd_tvd_params &p, int n) = 0;
+    virtual void gsres(const sporco_amd_tvd_params &p, double *out_host) = 0;
+    virtual void ystep(const sporco_amd_tvd_params &p, double *out_host) = 0;
+    virtual void adjoint() = 0;
+    Profiler prof;
+};
+TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, int device, void *stream);
+
 // the one place that instantiates Csc<float> / Csc<double> (csc_api.hip)
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream,
                   int depth = 1);
@@ -321,6 +340,11 @@ struct sporco_amd_csc {
     ~sporco_amd_csc() {
         if (stats_dev) (void)hipFree(stats_dev);
     }
+};
+
+struct sporco_amd_tvd {
+    std::unique_ptr<sporco_amd::TvdBase> impl;
+    int device;
 };
 
 #define SA_API_BEGIN try {

@@ -126,6 +126,11 @@ template <typename T> void prim_axpby(int64_t n, double a, const void *x, double
     SA_HIP(hipDeviceSynchronize());
 }
 
+template <typename T> void prim_mul(int64_t n, const void *x, const void *y, void *out) {
+    launch_tvd_mul<T>(nullptr, static_cast<const T *>(x), static_cast<const T *>(y), static_cast<T *>(out), n);
+    SA_HIP(hipDeviceSynchronize());
+}
+
 template <typename T>
 void prim_solvedbi_sm(int64_t npix, int64_t CN, int K, const void *ah, double rho, const void *b,
                       void *x) {
@@ -346,6 +351,12 @@ int sporco_amd_dev_axpby(int dtype, int64_t n, double a, const void *x, double b
     SA_API_BEGIN
     SA_REQUIRE(x && out && n >= 1, "bad argument");
     SA_DISPATCH(dtype, prim_axpby, n, a, x, b, y, out)
+    SA_API_END
+}
+int sporco_amd_dev_mul(int dtype, int64_t n, const void *x, const void *y, void *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(x && y && out && n >= 1, "bad argument");
+    SA_DISPATCH(dtype, prim_mul, n, x, y, out)
     SA_API_END
 }
 int sporco_amd_tikhonov_filter_dev(int dtype, int32_t H, int32_t W, int64_t P, const void *s_dev,

@@ -5,7 +5,7 @@ rank 4; the reference's examples/scripts/csc/cbpdn_gry.py pipeline).
 A :class:`DeviceArray` is a contiguous real array in device memory with a NumPy-like shape and
 dtype.  ``DeviceArray.from_host(a)`` uploads, ``x.get()`` (or ``numpy.asarray(x)``) downloads;
 :func:`sporco_amd.signal.tikhonov_filter`, :func:`sporco_amd.fft.fftconv` and the solver
-constructors accept and return them; ``x + y`` / ``x - y`` run on the device.
+constructors accept and return them; ``x + y`` / ``x - y`` / ``x * y`` run on the device.
 """
 
 import ctypes
@@ -101,6 +101,15 @@ class DeviceArray(object):
         return self._axpby(1.0, -1.0, other)
 
     def __mul__(self, scalar):
+        """By a scalar, or elementwise by a DeviceArray of the same shape and dtype."""
+        if isinstance(scalar, DeviceArray):
+            if scalar.shape != self.shape or scalar.dtype != self.dtype:
+                raise TypeError("device arithmetic needs a DeviceArray of the same shape and dtype")
+            out = DeviceArray(self.shape, self.dtype)
+            _lib.check(_lib.lib().sporco_amd_dev_mul(_lib.dtype_code(self.dtype), self.size,
+                                                     ctypes.c_void_p(self.ptr), ctypes.c_void_p(scalar.ptr),
+                                                     ctypes.c_void_p(out.ptr)))
+            return out
         out = DeviceArray(self.shape, self.dtype)
         _lib.check(_lib.lib().sporco_amd_dev_axpby(_lib.dtype_code(self.dtype), self.size,
                                                    float(scalar), ctypes.c_void_p(self.ptr), 0.0,
