@@ -392,6 +392,8 @@ typedef struct {
                                     no sparse coding call fills)                            */
 #define SPORCO_AMD_OUT_R02 14    /* pdl1_iter: block 0's |AXnr - y0 - s|^2 (l1l1_iter keeps it in OUT_L21, which
                                     the joint class needs for its l2,1 sum)                 */
+#define SPORCO_AMD_OUT_C2 12     /* tvl1 handles: ||c||^2 = ||S||^2 of the primal normaliser (the slot of CNSTR, which
+                                    no TVL1Denoise call writes); formed once, when S is uploaded */
 #define SPORCO_AMD_OUT_RGRX 15   /* l1l1_iter: what OUT_RGR is to ConvBPDNGradReg -- the two-block
                                     classes keep block 0's |AXnr|^2 in OUT_RGR                */
 #define SPORCO_AMD_OUT_COUNT 16
@@ -1082,6 +1084,23 @@ typedef struct {
 } sporco_amd_tvd_params;
 int sporco_amd_tvd_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv,
                           int device, void *stream, sporco_amd_tvd_t *out);
+/* l1-TV denoising, sporco.admm.tvl1.TVL1Denoise (sporco/admm/tvl1.py:27-399):
+ *     minimise ||Wdf (x - s)||_1 + lmbda ||Wtv sqrt((G_0 x)^2 + (G_1 x)^2)||_1
+ * by ADMM on (G_0; G_1; I) x - (y_0; y_1; y_d) = (0; 0; s).  The same arguments as sporco_amd_tvd_create; the
+ * handle is a sporco_amd_tvd_t in l1 mode and every sporco_amd_tvd_* call serves it, with these differences:
+ *   TVD_Y, TVD_U   are real (3,H,W,P): the two gradient blocks, then the data block;
+ *   tvd_sweeps     tvl1.py:240-260: the sweep with rho = 1 and a unit DFidWeight on P = A^T (Y - u_scale U),
+ *                  A^T including the identity block (p->rho and the DFidWeight do not enter);
+ *   tvd_gsres      the norms of linalg.rrs(G^T G X + X, P + S);
+ *   tvd_ystep      Y_g = prox_l2(AX_g + U_g, (lmbda / rho) Wtv), Y_d = prox_l1(AX_d + U_d - S, Wdf / rho) with
+ *                  AX_d = rlx X + (1 - rlx) (Y_d + S), U += AX - Y - c.  out: OUT_R2 = ||(G X - Y_g; X - Y_d - S)||^2,
+ *                  OUT_AX2 = ||(G X; X)||^2, OUT_Y2 = ||Y||^2, OUT_C2 = ||S||^2, OUT_S2 = ||A^T U||^2 and
+ *                  OUT_U2 = ||U||^2 over the three blocks (tvl1.py:362-372; rho applied by the host),
+ *                  OUT_DFID = sum |Wdf g_d| and OUT_L21 = sum Wtv sqrt(sum g_g^2), g = Y with geval_y, else
+ *                  (G X; X - S); OUT_XRRS_* as for tvd_gsres.  There is no Y - Yprev in this problem.
+ * The profiler names its two kernels tvl1_ystep and tvl1_adjoint. */
+int sporco_amd_tvl1_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv,
+                           int device, void *stream, sporco_amd_tvd_t *out);
 int sporco_amd_tvd_destroy(sporco_amd_tvd_t h);
 int sporco_amd_tvd_sync(sporco_amd_tvd_t h);
 /* The launch plan: out = (V, items per row, strips, rows per segment, segments, columns a strip covers);

@@ -56,7 +56,8 @@ OUT_XRRS_D2, OUT_XRRS_AX2, OUT_XRRS_B2 = 8, 9, 10
 OUT_RGR = 11
 OUT_CNSTR = 12
 OUT_CGIT, OUT_CGN = 13, 14
-OUT_R02 = 14                   # pdl1_iter: block 0's |AXnr - y0 - s|^2
+OUT_C2 = 12                    # tvl1 handles: ||S||^2 of the primal normaliser
+OUT_R02 = 14                 # pdl1_iter: block 0's |AXnr - y0 - s|^2
 OUT_SN2, OUT_RGRX = 14, 15      # l1l1_iter: |A^T u|^2, and RegGrad's sum beside block 0's use of OUT_RGR
 OUT_COUNT = 16
 
@@ -104,7 +105,7 @@ EXPORTS = (
     'sporco_amd_inner', 'sporco_amd_prox_l1', 'sporco_amd_prox_l1w', 'sporco_amd_prox_sl1l2',
     'sporco_amd_proj_l2', 'sporco_amd_proj_l1', 'sporco_amd_rfl2norm2',
     'sporco_amd_dev_mul',
-    'sporco_amd_tvd_create', 'sporco_amd_tvd_destroy', 'sporco_amd_tvd_sync', 'sporco_amd_tvd_plan',
+    'sporco_amd_tvd_create', 'sporco_amd_tvl1_create', 'sporco_amd_tvd_destroy', 'sporco_amd_tvd_sync', 'sporco_amd_tvd_plan',
     'sporco_amd_tvd_upload', 'sporco_amd_tvd_download', 'sporco_amd_tvd_sweeps', 'sporco_amd_tvd_gsres',
     'sporco_amd_tvd_ystep', 'sporco_amd_tvd_adjoint', 'sporco_amd_tvd_profile', 'sporco_amd_tvd_profile_read',
 )
@@ -379,6 +380,7 @@ def load(path=None):
         'sporco_amd_rfl2norm2': [ctypes.c_int, i32, i32, i64, vp, dptr],
         'sporco_amd_dev_mul': [ctypes.c_int, i64, vp, vp, vp],
         'sporco_amd_tvd_create': [ctypes.c_int, i32, i32, i64, i32, i32, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_tvl1_create': [ctypes.c_int, i32, i32, i64, i32, i32, ctypes.c_int, vp, ctypes.POINTER(vp)],
         'sporco_amd_tvd_destroy': [vp], 'sporco_amd_tvd_sync': [vp],
         'sporco_amd_tvd_plan': [vp, ctypes.POINTER(i64)],
         'sporco_amd_tvd_upload': [vp, ctypes.c_int, vp, ctypes.c_int],
@@ -1137,15 +1139,17 @@ class Solver(object):
 class TvdHandle(object):
     """Owner of one device-side TVL2Denoise problem (sporco_amd_tvd_*): arrays of shape
     (H, W, P); ``vector_tv``: the l2 norm of the y step also runs over the first of the trailing axes
-    (``C`` channels)."""
+    (``C`` channels).  ``l1``: a TVL1Denoise problem (sporco_amd_tvl1_create) -- Y and U have three
+    blocks, the last the data block."""
 
-    def __init__(self, H, W, P, dtype, C=1, vector_tv=False, device=0, stream=None):
+    def __init__(self, H, W, P, dtype, C=1, vector_tv=False, device=0, stream=None, l1=False):
         self.dims = (int(H), int(W), int(P))
         self.dtype = np.dtype(dtype)
+        self.blocks = 3 if l1 else 2
         h = ctypes.c_void_p()
-        check(lib().sporco_amd_tvd_create(dtype_code(dtype), int(H), int(W), int(P), int(C),
-                                          1 if vector_tv else 0, int(device), ctypes.c_void_p(stream or 0),
-                                          ctypes.byref(h)))
+        create = lib().sporco_amd_tvl1_create if l1 else lib().sporco_amd_tvd_create
+        check(create(dtype_code(dtype), int(H), int(W), int(P), int(C), 1 if vector_tv else 0, int(device),
+                     ctypes.c_void_p(stream or 0), ctypes.byref(h)))
         self._h = h
         self._lib = lib()
 
@@ -1171,7 +1175,7 @@ class TvdHandle(object):
         return dict(zip(('V', 'items', 'strips', 'R', 'nseg', 'TW'), (int(v) for v in out)))
 
     def var_shape(self, var):
-        return ((2,) if var in (TVD_Y, TVD_U) else ()) + self.dims
+        return ((self.blocks,) if var in (TVD_Y, TVD_U) else ()) + self.dims
 
     def upload(self, var, a):
         """``a``: a host array, a device pointer (int) of an array of the variable's size, or None

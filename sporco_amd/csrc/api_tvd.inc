@@ -1,11 +1,15 @@
 // api_tvd.inc -- the handle of TVL2Denoise (sporco/admm/tvl2.py:27-372; kernels: csc_tvd.h).  Unlike the
 // other api_*.inc files this one is included by csc_api.hip at namespace scope, BELOW template Csc<T>:
 // the class has no dictionary and no transform and does not share a CSC solver's state.
+// l1 mode (sporco_amd_tvl1_create): TVL1Denoise (sporco/admm/tvl1.py:27-399) -- three blocks in Y and U, no
+// dY, the y step and the adjoint are the tvl1_* kernels, the sweeps run with rho = 1 and a unit DFidWeight.
 template <typename T> struct Tvd : TvdBase {
     int device;
     hipStream_t st = nullptr;
     bool own_stream = false;
     TvdPlan pl;
+    const bool l1;
+    const int nb;                   // blocks of Y and of U: 2, or 3 in l1 mode
     int64_t E;                      // H W P
     T *s = nullptr, *x[2] = {nullptr, nullptr}, *y = nullptr, *u = nullptr, *dy = nullptr, *pd = nullptr, *q = nullptr;
     T *wdf = nullptr, *wtv = nullptr;
@@ -13,7 +17,8 @@ template <typename T> struct Tvd : TvdBase {
     int cur = 0;                    // x[cur] is X
     double *part_a = nullptr, *part_b = nullptr, *out_dev = nullptr, *out_pinned = nullptr;
 
-    Tvd(int H, int W, int64_t P, int C, bool vtv, int dev, void *stream) : device(dev) {
+    Tvd(int H, int W, int64_t P, int C, bool vtv, bool l1_mode, int dev, void *stream)
+        : device(dev), l1(l1_mode), nb(l1_mode ? 3 : 2) {
         SA_HIP(hipSetDevice(device));
         pl = tvd_plan(sizeof(T), H, W, P, C, vtv);
         E = pl.L * H;
@@ -25,7 +30,8 @@ template <typename T> struct Tvd : TvdBase {
         }
         prof.st = st;
         for (T **p : {&s, &x[0], &x[1], &pd, &q}) alloc_zero(p, E);
-        for (T **p : {&y, &u, &dy}) alloc_zero(p, 2 * E);
+        for (T **p : {&y, &u}) alloc_zero(p, nb * E);
+        if (!l1) alloc_zero(&dy, 2 * E);
         SA_HIP(hipMalloc((void **)&part_a, sizeof(double) * kTvdSums * pl.blocks()));
         SA_HIP(hipMalloc((void **)&part_b, sizeof(double) * kTvdSums * pl.blocks()));
         SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
@@ -59,7 +65,7 @@ template <typename T> struct Tvd : TvdBase {
     }
 
     T *var_buf(int var, int64_t *n) {
-        *n = (var == SPORCO_AMD_TVD_Y || var == SPORCO_AMD_TVD_U) ? 2 * E : E;
+        *n = (var == SPORCO_AMD_TVD_Y || var == SPORCO_AMD_TVD_U) ? nb * E : E;
         switch (var) {
         case SPORCO_AMD_TVD_S: return s;
         case SPORCO_AMD_TVD_X: return x[cur];
@@ -83,8 +89,17 @@ template <typename T> struct Tvd : TvdBase {
         int64_t n;
         T *dst = var_buf(var, &n);
         SA_HIP(hipMemcpyAsync(dst, src, sizeof(T) * n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        if (var == SPORCO_AMD_TVD_S)
+        if (var == SPORCO_AMD_TVD_S) {
             SA_HIP(hipMemcpyAsync(x[cur], s, sizeof(T) * n, hipMemcpyDeviceToDevice, st));
+            if (l1) {
+                // || c ||^2 = || S ||^2 of the primal normaliser is constant: formed here, on the device, into a
+                // slot of out_dev that no later finalize writes, so every read of the sums carries it
+                launch_tvl1_s2<T>(st, s, pl, part_a);
+                const int slot = SPORCO_AMD_OUT_C2;
+                const double one = 1.0;
+                launch_finalize(st, part_a, (int)pl.blocks(), 1, 1, &slot, &one, false, out_dev);
+            }
+        }
         sync();      // (the source may be pageable host memory, or a device array the caller frees next)
     }
     void download(int var, void *dst, bool on_device) override {
@@ -127,7 +142,13 @@ template <typename T> struct Tvd : TvdBase {
     void sweeps(const sporco_amd_tvd_params &p, int n) override {
         for (int i = 0; i < n; ++i) {
             ProfScope ps(prof, PS_TVD_SWEEP);
-            launch_tvd_sweep<T>(st, args(p), pl);
+            TvdArgs<T> a = args(p);
+            if (l1) {      // (tvl1.py:252-253: GaussSeidelStep with rho = 1 and W2 = 1)
+                a.rho = T(1);
+                a.wdf = nullptr;
+                a.wdf_s = T(1);
+            }
+            launch_tvd_sweep<T>(st, a, pl);
             cur ^= 1;
         }
     }
@@ -135,8 +156,9 @@ template <typename T> struct Tvd : TvdBase {
         TvdArgs<T> a = args(p);
         a.partials = part_a;
         {
-            ProfScope ps(prof, PS_TVD_YSTEP);
-            launch_tvd_ystep<T>(st, a, pl, true);
+            ProfScope ps(prof, l1 ? PS_TVL1_YSTEP : PS_TVD_YSTEP);
+            if (l1) launch_tvl1_ystep<T>(st, a, pl, true);
+            else launch_tvd_ystep<T>(st, a, pl, true);
         }
         const int slots[3] = {SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2};
         const double scales[3] = {1, 1, 1};
@@ -150,13 +172,15 @@ template <typename T> struct Tvd : TvdBase {
         TvdArgs<T> a = args(p);
         a.partials = part_a;
         {
-            ProfScope ps(prof, PS_TVD_YSTEP);
-            launch_tvd_ystep<T>(st, a, pl, false);
+            ProfScope ps(prof, l1 ? PS_TVL1_YSTEP : PS_TVD_YSTEP);
+            if (l1) launch_tvl1_ystep<T>(st, a, pl, false);
+            else launch_tvd_ystep<T>(st, a, pl, false);
         }
         a.partials = part_b;
         {
-            ProfScope ps(prof, PS_TVD_ADJOINT);
-            launch_tvd_adjoint<T>(st, a, pl);
+            ProfScope ps(prof, l1 ? PS_TVL1_ADJOINT : PS_TVD_ADJOINT);
+            if (l1) launch_tvl1_adjoint<T>(st, a, pl);
+            else launch_tvd_adjoint<T>(st, a, pl);
         }
         const int slots_a[8] = {SPORCO_AMD_OUT_R2,  SPORCO_AMD_OUT_AX2,     SPORCO_AMD_OUT_Y2,       SPORCO_AMD_OUT_DFID,
                                 SPORCO_AMD_OUT_L21, SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2};
@@ -174,13 +198,14 @@ template <typename T> struct Tvd : TvdBase {
         TvdArgs<T> a = args(p);
         a.partials = part_b;
         // (dY is whatever the last y step left, or zero: its sum is not read)
-        ProfScope ps(prof, PS_TVD_ADJOINT);
-        launch_tvd_adjoint<T>(st, a, pl);
+        ProfScope ps(prof, l1 ? PS_TVL1_ADJOINT : PS_TVD_ADJOINT);
+        if (l1) launch_tvl1_adjoint<T>(st, a, pl);
+        else launch_tvd_adjoint<T>(st, a, pl);
     }
 };
 
-TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, int device, void *stream) {
-    if (dtype == SPORCO_AMD_F32) return new Tvd<float>(H, W, P, C, vector_tv, device, stream);
-    if (dtype == SPORCO_AMD_F64) return new Tvd<double>(H, W, P, C, vector_tv, device, stream);
+TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, bool l1, int device, void *stream) {
+    if (dtype == SPORCO_AMD_F32) return new Tvd<float>(H, W, P, C, vector_tv, l1, device, stream);
+    if (dtype == SPORCO_AMD_F64) return new Tvd<double>(H, W, P, C, vector_tv, l1, device, stream);
     throw Error(SPORCO_AMD_EINVAL, "dtype must be SPORCO_AMD_F32 or SPORCO_AMD_F64");
 }

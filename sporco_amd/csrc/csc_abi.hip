@@ -853,7 +853,23 @@ int sporco_amd_tvd_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C,
     SA_REQUIRE(device >= 0 && device < n, "device index out of range");
     std::unique_ptr<sporco_amd_tvd> h(new sporco_amd_tvd);
     h->device = device;
-    h->impl.reset(make_tvd(dtype, H, W, P, C, vector_tv != 0, device, stream));
+    h->impl.reset(make_tvd(dtype, H, W, P, C, vector_tv != 0, false, device, stream));
+    *out = h.release();
+    SA_API_END
+}
+
+int sporco_amd_tvl1_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int device,
+                           void *stream, sporco_amd_tvd_t *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out != nullptr, "null argument");
+    SA_REQUIRE(H >= 2 && W >= 2 && P >= 1 && C >= 1, "tvl1: H, W >= 2, P, C >= 1");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    std::unique_ptr<sporco_amd_tvd> h(new sporco_amd_tvd);
+    h->device = device;
+    h->impl.reset(make_tvd(dtype, H, W, P, C, vector_tv != 0, true, device, stream));
     *out = h.release();
     SA_API_END
 }

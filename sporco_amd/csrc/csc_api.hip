@@ -34,7 +34,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "pdl1_solve",       "pdl1_dual",
                                     "projl1_search",    "projl1_apply",
                                     "projl1_pass0",     "projl1_cnstr",
-                                    "tvd_sweep",        "tvd_ystep",        "tvd_adjoint"};
+                                    "tvd_sweep",        "tvd_ystep",        "tvd_adjoint",
+                                    "tvl1_ystep",       "tvl1_adjoint"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and

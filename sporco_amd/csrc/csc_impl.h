@@ -114,6 +114,8 @@ enum ProfSlot {
     PS_TVD_SWEEP,               // TVL2Denoise: one Jacobi sweep of the x step (csc_tvd.h)
     PS_TVD_YSTEP,               // ... relax + y step + u step + the sums that need X
     PS_TVD_ADJOINT,             // ... A^T (Y - U), A^T U and the dual-residual sums
+    PS_TVL1_YSTEP,              // TVL1Denoise: relax + y step + u step of the three blocks + the sums that need X
+    PS_TVL1_ADJOINT,            // ... A^T (Y - U), A^T U with the identity block, || A^T U ||^2 and || U ||^2
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -310,7 +312,8 @@ static bool var_is_valid(int var) {
            (var >= SPORCO_AMD_VAR_DX && var < SPORCO_AMD_VAR_COUNT);
 }
 
-// The handle of TVL2Denoise (api_tvd.inc): the arrays of one (H, W, P) problem and a stream.
+// The handle of TVL2Denoise and, in its l1 mode, TVL1Denoise (api_tvd.inc): the arrays of one (H, W, P)
+// problem and a stream.
 struct TvdBase {
     virtual ~TvdBase() {}
     virtual void sync() = 0;
@@ -323,7 +326,7 @@ struct TvdBase {
     virtual void adjoint() = 0;
     Profiler prof;
 };
-TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, int device, void *stream);
+TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, bool l1, int device, void *stream);
 
 // the one place that instantiates Csc<float> / Csc<double> (csc_api.hip)
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream,

@@ -62,7 +62,7 @@ template <typename T> struct TvdArgs {
     const T *s = nullptr;      // the signal
     const T *xin = nullptr;    // X (the sweep's source)
     T *xout = nullptr;         // tvd_sweep: the new X
-    T *y = nullptr, *u = nullptr, *dy = nullptr;   // two blocks each
+    T *y = nullptr, *u = nullptr, *dy = nullptr;   // two blocks each (tvl1_*: three of y and u, no dy)
     T *pd = nullptr, *q = nullptr;                 // A^T (Y - U), A^T U
     const T *wdf = nullptr;    // DFidWeight array of S's shape, or nullptr: wdf_s
     const T *wtv = nullptr;    // TVWeight array of S's shape, or nullptr: wtv_s
@@ -82,6 +82,28 @@ template <typename T> void launch_tvd_sweep(hipStream_t st, const TvdArgs<T> &a,
 template <typename T> void launch_tvd_ystep(hipStream_t st, const TvdArgs<T> &a, const TvdPlan &pl, bool res_only);
 // partials[0..1] = sum (A^T dY)^2, sum (A^T U)^2.
 template <typename T> void launch_tvd_adjoint(hipStream_t st, const TvdArgs<T> &a, const TvdPlan &pl);
+
+// l1-TV denoising, sporco.admm.tvl1.TVL1Denoise (sporco/admm/tvl1.py:27-399),
+//     minimise || Wdf (x - s) ||_1 + lmbda || Wtv sqrt((G_0 x)^2 + (G_1 x)^2) ||_1,
+// by ADMM on (G_0; G_1; I) x - (y_0; y_1; y_d) = (0; 0; s): the same items, strips and segments, a third
+// (data) block of Y and U at 2 E, and no dY -- the dual residual is rho || A^T U || (tvl1.py:362-372).
+// One iteration (MaxGSIter = 2): tvd_sweep, tvd_sweep, tvl1_ystep, tvl1_adjoint.  The x step
+// (tvl1.py:240-260) is GaussSeidelStep with rho = 1, W2 = 1 on S + (Y_d - U_d) and G^T (Y_g - U_g): with
+// PD = A^T (Y - U) = G^T (Y_g - U_g) + (Y_d - U_d) and Q = A^T U = G^T U_g + U_d including the identity
+// block it is tvd_sweep as it stands, called with rho = 1, wdf = nullptr, wdf_s = 1.
+//
+// partials[0..7] = sum (AXnr - Y - c)^2, sum AXnr^2, sum Y^2 over the three blocks (AXnr = (G X; X),
+// c = (0; 0; S)), sum |Wdf g_d|, sum Wtv sqrt(sum g_g^2) (g = Y with geval_y, else (G X; X - S)), and
+// |ax - b|^2, |ax|^2, |b|^2 of linalg.rrs(G^T G X + X, P + S) (tvl1.py:254-257).  The y step of the data
+// block is prox_l1(AX_d + U_d - S, Wdf / rho): Wdf enters linearly, a zero weight leaves the value as it is.
+// res_only: only the last three, nothing written.
+template <typename T> void launch_tvl1_ystep(hipStream_t st, const TvdArgs<T> &a, const TvdPlan &pl, bool res_only);
+// PD, Q with the identity block; partials[0..1] = sum (A^T U)^2, sum U^2 over the three blocks.
+template <typename T> void launch_tvl1_adjoint(hipStream_t st, const TvdArgs<T> &a, const TvdPlan &pl);
+// partials[b] = the part of sum s^2 of workgroup b, b < pl.blocks() (|| c ||^2 of the primal normaliser,
+// formed once when S is set)
+template <typename T> void launch_tvl1_s2(hipStream_t st, const T *s, const TvdPlan &pl, double *partials);
+
 // out = x * y, elementwise (DeviceArray * DeviceArray)
 template <typename T> void launch_tvd_mul(hipStream_t st, const T *x, const T *y, T *out, int64_t n);
 

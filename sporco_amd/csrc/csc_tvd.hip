@@ -1,5 +1,5 @@
-// csc_tvd.hip -- the kernels of csc_tvd.h: tvd_sweep, tvd_ystep, tvd_adjoint (and the elementwise product
-// of two device arrays).  float32 / float64, any H, W >= 2, any number of planes; vector TV over up to
+// csc_tvd.hip -- the kernels of csc_tvd.h: tvd_sweep, tvd_ystep, tvd_adjoint, their three-block forms
+// tvl1_ystep, tvl1_adjoint (and the elementwise product of two device arrays).  float32 / float64, any H, W >= 2, any number of planes; vector TV over up to
 // kTvdMaxChannels channels.
 #include "csc_tvd.h"
 #include "csc_kernels_dev.h"
@@ -355,6 +355,197 @@ __global__ void __launch_bounds__(kTvdThreads) tvd_adjoint_kernel(const TvdKArgs
     block_sum_store<kTvdSums>(acc, dyn_lds<double>(), a.partials + blk * kTvdSums);
 }
 
+template <typename T> __device__ __forceinline__ T tvd_abs(T v) { return v < T(0) ? -v : v; }
+// prox_l1: sign(v) max(0, |v| - alpha) (sporco/prox/_lp.py:144-183)
+template <typename T> __device__ __forceinline__ T tvd_soft(T v, T alpha) {
+    const T b = tvd_abs(v) - alpha;
+    return b > T(0) ? (v < T(0) ? -b : b) : T(0);
+}
+
+// tvd_ystep for the three-block constraint (G_0; G_1; I) x - y = (0; 0; s): the same row walk, the data
+// block of Y and U at 2 E, no dY.
+template <typename T, int G, bool VTV, bool RES>
+__global__ void __launch_bounds__(kTvdThreads) tvl1_ystep_kernel(const TvdKArgs<T> ka) {
+    const TvdArgs<T> &a = ka.a;
+    const TvdPlan &pl = ka.pl;
+    TvdItem<T, G, VTV> it;
+    it.init(pl);
+    const int ys = (int)blockIdx.y * pl.rows, ye = ys + pl.rows < pl.H ? ys + pl.rows : pl.H;
+    const int64_t L = pl.L, E = L * pl.H;
+    const bool relax = a.rlx != T(1);
+    const T rl1 = T(1) - a.rlx;
+    const T irho = T(1) / a.rho;
+    double acc[kTvdSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (it.ok) {
+        T up[G], cur[G], dn[G];
+        tvd_zero<G>(up);
+        if (ys > 0) it.load(a.xin + (int64_t)(ys - 1) * L, up);
+        it.load(a.xin + (int64_t)ys * L, cur);
+        for (int y = ys; y < ye; ++y) {
+            const int64_t ro = (int64_t)y * L;
+            const bool top = y == 0, bottom = y + 1 == pl.H;
+            tvd_zero<G>(dn);
+            if (!bottom) it.load(a.xin + ro + L, dn);
+            T l[G], r[G], p[G], s[G], a0[G], a1[G];
+            it.template sides<true>(a.xin + ro, pl.P, l, r);
+            tvd_load_p<T, G, VTV>(a, it, ro, p);
+            it.load(a.s + ro, s);
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                if (!it.has(j)) continue;
+                a0[j] = bottom ? T(0) : dn[j] - cur[j];
+                a1[j] = it.is_last(j) ? T(0) : r[j] - cur[j];
+                // A^T A X = G^T G X + X against A^T (c + Y - U) = P + S
+                const T ata = ((top ? T(0) : cur[j] - up[j]) - a0[j]) + ((it.is_first(j) ? T(0) : cur[j] - l[j]) - a1[j]);
+                const T axv = ata + cur[j], bv = p[j] + s[j];
+                const double d = (double)(axv - bv);
+                acc[5] += d * d;
+                acc[6] += (double)axv * (double)axv;
+                acc[7] += (double)bv * (double)bv;
+            }
+            if (!RES) {
+                T y0[G], y1[G], yd[G], u0[G], u1[G], ud[G], wt[G], wd[G];
+                it.load(a.y + ro, y0);
+                it.load(a.y + E + ro, y1);
+                it.load(a.y + 2 * E + ro, yd);
+                it.load(a.u + ro, u0);
+                it.load(a.u + E + ro, u1);
+                it.load(a.u + 2 * E + ro, ud);
+                if (a.wtv) it.load(a.wtv + ro, wt);
+                if (a.wdf) it.load(a.wdf + ro, wd);
+                T n2[G], grp = T(0);
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    n2[j] = T(0);
+                    if (!it.has(j)) continue;
+                    // AX = rlx AXnr + (1 - rlx) (Y + c), v = AX + U (u0, u1, ud become v)
+                    const T x0 = relax ? a.rlx * a0[j] + rl1 * y0[j] : a0[j];
+                    const T x1 = relax ? a.rlx * a1[j] + rl1 * y1[j] : a1[j];
+                    const T xd = relax ? a.rlx * cur[j] + rl1 * (yd[j] + s[j]) : cur[j];
+                    u0[j] = x0 + a.u_scale * u0[j];
+                    u1[j] = x1 + a.u_scale * u1[j];
+                    ud[j] = xd + a.u_scale * ud[j];
+                    n2[j] = u0[j] * u0[j] + u1[j] * u1[j];
+                    grp += n2[j];
+                }
+                T gsum = T(0);
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    if (!it.has(j)) continue;
+                    const T wtj = (!VTV && a.wtv) ? wt[j] : a.wtv_s;
+                    const T wdj = a.wdf ? wd[j] : a.wdf_s;
+                    const T sc = tvd_shrink(tvd_sqrt(VTV ? grp : n2[j]), a.thr * wtj);
+                    const T yn0 = sc * u0[j], yn1 = sc * u1[j];
+                    // the data block: Y_d = prox_l1(AX_d + U_d - S, Wdf / rho), U_d += AX_d - Y_d - S
+                    const T vd = ud[j] - s[j];
+                    const T ynd = tvd_soft(vd, irho * wdj);
+                    u0[j] -= yn0;
+                    u1[j] -= yn1;
+                    ud[j] = vd - ynd;
+                    y0[j] = yn0;
+                    y1[j] = yn1;
+                    yd[j] = ynd;
+                    const T xs = cur[j] - s[j];
+                    const double r0 = (double)(a0[j] - yn0), r1 = (double)(a1[j] - yn1), rd = (double)(xs - ynd);
+                    acc[0] += (r0 * r0 + r1 * r1) + rd * rd;
+                    acc[1] += ((double)a0[j] * (double)a0[j] + (double)a1[j] * (double)a1[j]) +
+                              (double)cur[j] * (double)cur[j];
+                    acc[2] += ((double)yn0 * (double)yn0 + (double)yn1 * (double)yn1) + (double)ynd * (double)ynd;
+                    acc[3] += (double)tvd_abs(wdj * (a.geval_y ? ynd : xs));
+                    const T g2 = a.geval_y ? yn0 * yn0 + yn1 * yn1 : a0[j] * a0[j] + a1[j] * a1[j];
+                    if (VTV) gsum += g2;
+                    else acc[4] += (double)(wtj * tvd_sqrt(g2));
+                }
+                if (VTV) acc[4] += (double)(a.wtv_s * tvd_sqrt(gsum));
+                it.store(a.y + ro, y0);
+                it.store(a.y + E + ro, y1);
+                it.store(a.y + 2 * E + ro, yd);
+                it.store(a.u + ro, u0);
+                it.store(a.u + E + ro, u1);
+                it.store(a.u + 2 * E + ro, ud);
+            }
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                up[j] = cur[j];
+                cur[j] = dn[j];
+            }
+        }
+    }
+    const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    block_sum_store<kTvdSums>(acc, dyn_lds<double>(), a.partials + blk * kTvdSums);
+}
+
+// tvd_adjoint with the identity block: PD = G^T (Y_g - U_g) + (Y_d - U_d), Q = G^T U_g + U_d, and the two
+// norms of the dual residual (tvl1.py:362-372): sum Q^2 and sum U^2 over every entry of the three blocks
+// (the last row of block 0 and the last column of block 1 do not enter the stencil but are part of U).
+template <typename T, int G, bool VTV>
+__global__ void __launch_bounds__(kTvdThreads) tvl1_adjoint_kernel(const TvdKArgs<T> ka) {
+    const TvdArgs<T> &a = ka.a;
+    const TvdPlan &pl = ka.pl;
+    TvdItem<T, G, VTV> it;
+    it.init(pl);
+    const int ys = (int)blockIdx.y * pl.rows, ye = ys + pl.rows < pl.H ? ys + pl.rows : pl.H;
+    const int64_t L = pl.L, E = L * pl.H;
+    double acc[kTvdSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (it.ok) {
+        // block 0 of Y - U and of U in the row above (0 above the image)
+        T zp[G], up[G];
+        tvd_zero<G>(zp);
+        tvd_zero<G>(up);
+        if (ys > 0) {
+            const int64_t rp = (int64_t)(ys - 1) * L;
+            T t[G];
+            it.load(a.y + rp, t);
+            it.load(a.u + rp, up);
+#pragma unroll
+            for (int j = 0; j < G; ++j) zp[j] = t[j] - up[j];
+        }
+        for (int y = ys; y < ye; ++y) {
+            const int64_t ro = (int64_t)y * L;
+            const bool bottom = y + 1 == pl.H;
+            T y0[G], u0[G], y1[G], u1[G], yd[G], ud[G], yl[G], ul[G], none[G];
+            tvd_zero<G>(y0);
+            if (!bottom) it.load(a.y + ro, y0);
+            it.load(a.u + ro, u0);
+            it.load(a.y + E + ro, y1);
+            it.load(a.u + E + ro, u1);
+            it.load(a.y + 2 * E + ro, yd);
+            it.load(a.u + 2 * E + ro, ud);
+            it.template sides<false>(a.y + E + ro, pl.P, yl, none);
+            it.template sides<false>(a.u + E + ro, pl.P, ul, none);
+            T pd[G], q[G];
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                pd[j] = q[j] = T(0);
+                if (!it.has(j)) continue;
+                acc[1] += ((double)u0[j] * (double)u0[j] + (double)u1[j] * (double)u1[j]) + (double)ud[j] * (double)ud[j];
+                const bool lastc = it.is_last(j);
+                const T u0c = bottom ? T(0) : u0[j];      // (the last row of G_0 is zero ...)
+                const T y1c = lastc ? T(0) : y1[j], u1c = lastc ? T(0) : u1[j];      // (... and the last column of G_1)
+                const T z0 = y0[j] - u0c;
+                pd[j] = ((zp[j] - z0) + ((yl[j] - ul[j]) - (y1c - u1c))) + (yd[j] - ud[j]);
+                q[j] = ((up[j] - u0c) + (ul[j] - u1c)) + ud[j];
+                acc[0] += (double)q[j] * (double)q[j];
+                zp[j] = z0;
+                up[j] = u0c;
+            }
+            it.store(a.pd + ro, pd);
+            it.store(a.q + ro, q);
+        }
+    }
+    const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    block_sum_store<kTvdSums>(acc, dyn_lds<double>(), a.partials + blk * kTvdSums);
+}
+
+// partials[block] = sum s^2 over the block's share of the n elements, in a fixed order
+template <typename T>
+__global__ void __launch_bounds__(kTvdThreads) tvl1_s2_kernel(const T *__restrict__ s, int64_t n, double *partials) {
+    double acc[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * kTvdThreads + (int)threadIdx.x; i < n; i += (int64_t)gridDim.x * kTvdThreads)
+        acc[0] += (double)s[i] * (double)s[i];
+    block_sum_store<1>(acc, dyn_lds<double>(), partials + blockIdx.x);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(kThreads) tvd_mul_kernel(const T *__restrict__ x, const T *__restrict__ y,
                                                            T *__restrict__ out, int64_t n) {
@@ -422,6 +613,28 @@ template <typename T> void launch_tvd_adjoint(hipStream_t st, const TvdArgs<T> &
     SA_TVD_DISPATCH(tvd_adjoint_kernel);
 }
 
+template <typename T> void launch_tvl1_ystep(hipStream_t st, const TvdArgs<T> &a, const TvdPlan &pl, bool res_only) {
+    SA_REQUIRE(a.s && a.xin && a.pd && a.q && a.partials, "tvl1_ystep: null argument");
+    SA_REQUIRE(res_only || (a.y && a.u), "tvl1_ystep: null argument");
+    SA_REQUIRE(!(pl.vtv && a.wtv), "tvl1_ystep: vector TV takes a scalar TVWeight");
+    const TvdKArgs<T> ka = tvd_kargs(a, pl);
+    if (res_only) SA_TVD_DISPATCH(tvl1_ystep_kernel, true);
+    else SA_TVD_DISPATCH(tvl1_ystep_kernel, false);
+}
+
+template <typename T> void launch_tvl1_adjoint(hipStream_t st, const TvdArgs<T> &a, const TvdPlan &pl) {
+    SA_REQUIRE(a.y && a.u && a.pd && a.q && a.partials, "tvl1_adjoint: null argument");
+    const TvdKArgs<T> ka = tvd_kargs(a, pl);
+    SA_TVD_DISPATCH(tvl1_adjoint_kernel);
+}
+
+template <typename T> void launch_tvl1_s2(hipStream_t st, const T *s, const TvdPlan &pl, double *partials) {
+    SA_REQUIRE(s && partials && pl.blocks() >= 1 && pl.blocks() < ((int64_t)1 << 31), "tvl1_s2: bad argument");
+    hipLaunchKernelGGL((tvl1_s2_kernel<T>), dim3((unsigned)pl.blocks()), dim3(kTvdThreads), kTvdLds, st, s,
+                       pl.L * pl.H, partials);
+    SA_HIP(hipGetLastError());
+}
+
 template <typename T> void launch_tvd_mul(hipStream_t st, const T *x, const T *y, T *out, int64_t n) {
     hipLaunchKernelGGL((tvd_mul_kernel<T>), dim3(grid_for(n)), dim3(kThreads), 0, st, x, y, out, n);
     SA_HIP(hipGetLastError());
@@ -431,6 +644,9 @@ template <typename T> void launch_tvd_mul(hipStream_t st, const T *x, const T *y
     template void launch_tvd_sweep<T>(hipStream_t, const TvdArgs<T> &, const TvdPlan &);               \
     template void launch_tvd_ystep<T>(hipStream_t, const TvdArgs<T> &, const TvdPlan &, bool);         \
     template void launch_tvd_adjoint<T>(hipStream_t, const TvdArgs<T> &, const TvdPlan &);             \
+    template void launch_tvl1_ystep<T>(hipStream_t, const TvdArgs<T> &, const TvdPlan &, bool);        \
+    template void launch_tvl1_adjoint<T>(hipStream_t, const TvdArgs<T> &, const TvdPlan &);            \
+    template void launch_tvl1_s2<T>(hipStream_t, const T *, const TvdPlan &, double *);                \
     template void launch_tvd_mul<T>(hipStream_t, const T *, const T *, T *, int64_t);
 SA_TVD_INST(float)
 SA_TVD_INST(double)
