@@ -1130,6 +1130,68 @@ int sporco_amd_tvd_profile(sporco_amd_tvd_t h, int enable);
 int sporco_amd_tvd_profile_read(sporco_amd_tvd_t h, int slot, const char **name, double *total_ms,
                                 int64_t *count);
 
+/* ---- TV deconvolution: sporco.admm.tvl2.TVL2Deconv (sporco/admm/tvl2.py:377-702) and
+ * sporco.admm.tvl1.TVL1Deconv (sporco/admm/tvl1.py:403-758) ------------------------------------------
+ *     l2:  minimise (1/2) ||H x - s||^2 + lmbda ||Wtv sqrt((G_0 x)^2 + (G_1 x)^2)||_1   on (G_0; G_1) x = y
+ *     l1:  minimise ||Wdf (H x - s)||_1 + lmbda ||Wtv sqrt((G_0 x)^2 + (G_1 x)^2)||_1   on (G_0; G_1; H) x - y = (0; 0; s)
+ * H the circular convolution with the kernel A, G_i the CIRCULAR difference (G_i x)[j] = x[j] - x[j - 1]
+ * (sporco/signal.py:204-240).  The x step is a pointwise solve between one forward and one inverse
+ * transform (rfft2 / irfft2 on the generic chain); the gradients, their adjoints, the y and u steps are
+ * periodic stencils (csrc/csc_tvdc.h).  The handle owns S, X, Y, U, the spectra of S and A, the work
+ * spectrum and the transform plans of H and W; a transform length that does not fit is refused at creation
+ * ("transform length too large").  vector_tv, C, P as for sporco_amd_tvd_create.  PA: the planes of the
+ * kernel A, P (one kernel per plane) or 1 (one for all).  Y, U start at zero. */
+typedef struct sporco_amd_tvdc *sporco_amd_tvdc_t;
+#define SPORCO_AMD_TVDC_S 0    /* real (H,W,P)     the signal                                             */
+#define SPORCO_AMD_TVDC_X 1    /* real (H,W,P)     the result of the x step (download only)               */
+#define SPORCO_AMD_TVDC_Y 2    /* real (nb,H,W,P)  the blocks of Y: nb = 2, or 3 in l1 mode (data block last) */
+#define SPORCO_AMD_TVDC_U 3    /* real (nb,H,W,P)  ... and of U (without a pending u_scale)               */
+#define SPORCO_AMD_TVDC_WDF 4  /* real (H,W,P)     l1: DFidWeight array (upload NULL: the scalar wdf)     */
+#define SPORCO_AMD_TVDC_WTV 5  /* real (H,W,P)     TVWeight array (upload NULL: the scalar wtv; not with vector_tv) */
+#define SPORCO_AMD_TVDC_HX 6   /* real (H,W,P)     l1: H X of the last x step (download only)             */
+typedef struct {
+    double rho, lmbda, rlx;
+    double u_scale;           /* pending U /= rsf (admm.py:573): the x and y steps apply it                 */
+    double wdf, wtv;          /* scalar weights, read where no array is set                                 */
+    int32_t geval_y;          /* RegTV (l1: and DFid) at Y, else at A X - c                                 */
+    int32_t lin_solve_check;  /* the x step also forms OUT_XRRS_*                                           */
+    int32_t want_rsdl;        /* the y step also forms the dual residual's sums (l2: and writes Y - Yprev)  */
+    int32_t want_stats;       /* l2: the x step also forms OUT_DFID                                         */
+} sporco_amd_tvdc_params;
+int sporco_amd_tvdc_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int64_t PA,
+                           int device, void *stream, sporco_amd_tvdc_t *out);
+int sporco_amd_tvl1dc_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int64_t PA,
+                             int device, void *stream, sporco_amd_tvdc_t *out);
+int sporco_amd_tvdc_destroy(sporco_amd_tvdc_t h);
+int sporco_amd_tvdc_sync(sporco_amd_tvdc_t h);
+/* The launch plan: out[0..5] as sporco_amd_tvd_plan for tvdc_ystep / tvdc_adjoint; out[6] = planes per access
+ * of tvdc_solve (2: 16 bytes in float32), out[7] = its workgroups. */
+int sporco_amd_tvdc_plan(sporco_amd_tvdc_t h, int64_t out[8]);
+/* Copy an array in or out; on_device: src / dst is a device pointer (no host traffic).  Uploading S also
+ * forms its spectrum (and AHSf, ||S||^2).  After Y or U have been written, sporco_amd_tvdc_adjoint must run
+ * before the next x step. */
+int sporco_amd_tvdc_upload(sporco_amd_tvdc_t h, int var, const void *src, int on_device);
+int sporco_amd_tvdc_download(sporco_amd_tvdc_t h, int var, void *dst, int on_device);
+/* The kernel: a real C-ordered (ah, aw, PA) array, ah <= H, aw <= W; zero-padded and transformed on the
+ * device (the phase of sporco.signal.fftconv), then |Af|^2 and AHSf = conj(Af) Sf. */
+int sporco_amd_tvdc_set_kernel(sporco_amd_tvdc_t h, const void *A, int32_t ah, int32_t aw, int on_device);
+/* The x step: Xf = (AHSf + rho F(G^T (Y - u_scale U))) / (|Af|^2 + rho GHGf), l1: Xf = (AHSf + F(G^T (Y_g -
+ * u_scale U_g)) + conj(Af) F(Y_d - u_scale U_d)) / (|Af|^2 + GHGf); X (l1: and H X) by one inverse transform. */
+int sporco_amd_tvdc_xstep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p);
+/* relax_AX + ystep + ustep in one launch, the adjoint arrays of the next x step in a second, and one host
+ * read.  out: OUT_R2 = ||A X - Y - c||^2, OUT_AX2, OUT_Y2, OUT_L21 = sum Wtv sqrt(sum g_g^2);
+ *   l2: OUT_DFID = ||H X - S||^2 by Parseval (not halved; from the x step), OUT_S2 = ||G^T (Y - Yprev)||^2,
+ *       OUT_U2 = ||G^T U||^2 (rho applied by the host);
+ *   l1: OUT_DFID = sum |Wdf g_d|, OUT_S2 = ||A^T U||^2 (over spectra), OUT_U2 = ||U||^2, OUT_C2 = ||S||^2;
+ *   OUT_XRRS_* with lin_solve_check.  U is stored with u_scale applied: the pending factor is 1 afterwards. */
+int sporco_amd_tvdc_ystep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p, double out[SPORCO_AMD_OUT_COUNT]);
+/* The adjoint arrays of the current Y, U (after an upload of either). */
+int sporco_amd_tvdc_adjoint(sporco_amd_tvdc_t h);
+/* Per-kernel event timing of the handle's launches, as sporco_amd_csc_profile / _profile_read. */
+int sporco_amd_tvdc_profile(sporco_amd_tvdc_t h, int enable);
+int sporco_amd_tvdc_profile_read(sporco_amd_tvdc_t h, int slot, const char **name, double *total_ms,
+                                 int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,10 @@ EXPORTS = (
     'sporco_amd_tvd_create', 'sporco_amd_tvl1_create', 'sporco_amd_tvd_destroy', 'sporco_amd_tvd_sync', 'sporco_amd_tvd_plan',
     'sporco_amd_tvd_upload', 'sporco_amd_tvd_download', 'sporco_amd_tvd_sweeps', 'sporco_amd_tvd_gsres',
     'sporco_amd_tvd_ystep', 'sporco_amd_tvd_adjoint', 'sporco_amd_tvd_profile', 'sporco_amd_tvd_profile_read',
+    'sporco_amd_tvdc_create', 'sporco_amd_tvl1dc_create', 'sporco_amd_tvdc_destroy', 'sporco_amd_tvdc_sync',
+    'sporco_amd_tvdc_plan', 'sporco_amd_tvdc_upload', 'sporco_amd_tvdc_download', 'sporco_amd_tvdc_set_kernel',
+    'sporco_amd_tvdc_xstep', 'sporco_amd_tvdc_ystep', 'sporco_amd_tvdc_adjoint', 'sporco_amd_tvdc_profile',
+    'sporco_amd_tvdc_profile_read',
 )
 
 
@@ -174,6 +178,17 @@ class TvdParams(ctypes.Structure):
 
 
 TVD_S, TVD_X, TVD_Y, TVD_U, TVD_WDF, TVD_WTV = range(6)
+
+
+class TvdcParams(ctypes.Structure):
+    """sporco_amd_tvdc_params: scalars of one TVL2Deconv / TVL1Deconv step."""
+    _fields_ = [('rho', ctypes.c_double), ('lmbda', ctypes.c_double), ('rlx', ctypes.c_double),
+                ('u_scale', ctypes.c_double), ('wdf', ctypes.c_double), ('wtv', ctypes.c_double),
+                ('geval_y', ctypes.c_int32), ('lin_solve_check', ctypes.c_int32), ('want_rsdl', ctypes.c_int32),
+                ('want_stats', ctypes.c_int32)]
+
+
+TVDC_S, TVDC_X, TVDC_Y, TVDC_U, TVDC_WDF, TVDC_WTV, TVDC_HX = range(7)
 
 REDUCE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
 EUNSUPPORTED = -5
@@ -390,6 +405,19 @@ def load(path=None):
         'sporco_amd_tvd_ystep': [vp, ctypes.POINTER(TvdParams), dptr],
         'sporco_amd_tvd_adjoint': [vp],
         'sporco_amd_tvd_profile': [vp, ctypes.c_int],
+        'sporco_amd_tvdc_create': [ctypes.c_int, i32, i32, i64, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_tvl1dc_create': [ctypes.c_int, i32, i32, i64, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_tvdc_destroy': [vp], 'sporco_amd_tvdc_sync': [vp],
+        'sporco_amd_tvdc_plan': [vp, ctypes.POINTER(i64)],
+        'sporco_amd_tvdc_upload': [vp, ctypes.c_int, vp, ctypes.c_int],
+        'sporco_amd_tvdc_download': [vp, ctypes.c_int, vp, ctypes.c_int],
+        'sporco_amd_tvdc_set_kernel': [vp, vp, i32, i32, ctypes.c_int],
+        'sporco_amd_tvdc_xstep': [vp, ctypes.POINTER(TvdcParams)],
+        'sporco_amd_tvdc_ystep': [vp, ctypes.POINTER(TvdcParams), dptr],
+        'sporco_amd_tvdc_adjoint': [vp],
+        'sporco_amd_tvdc_profile': [vp, ctypes.c_int],
+        'sporco_amd_tvdc_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
+                                         ctypes.POINTER(ctypes.c_int64)],
         'sporco_amd_tvd_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                         ctypes.POINTER(i64)],
     }
@@ -1226,6 +1254,106 @@ class TvdHandle(object):
             name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
             check(self._lib.sporco_amd_tvd_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
                                                         ctypes.byref(cnt)))
+            if cnt.value:
+                res[name.value.decode()] = (ms.value, cnt.value)
+        return res
+
+
+class TvdcHandle(object):
+    """Owner of one device-side TVL2Deconv problem (sporco_amd_tvdc_*), or with ``l1`` of a TVL1Deconv
+    problem (sporco_amd_tvl1dc_create: Y and U have three blocks, the last the data block).  Arrays of
+    shape (H, W, P); ``PA``: the planes of the kernel A, ``P`` or 1."""
+
+    def __init__(self, H, W, P, dtype, C=1, vector_tv=False, PA=1, device=0, stream=None, l1=False):
+        self.dims = (int(H), int(W), int(P))
+        self.PA = int(PA)
+        self.dtype = np.dtype(dtype)
+        self.blocks = 3 if l1 else 2
+        h = ctypes.c_void_p()
+        create = lib().sporco_amd_tvl1dc_create if l1 else lib().sporco_amd_tvdc_create
+        check(create(dtype_code(dtype), int(H), int(W), int(P), int(C), 1 if vector_tv else 0, int(PA), int(device),
+                     ctypes.c_void_p(stream or 0), ctypes.byref(h)))
+        self._h = h
+        self._lib = lib()
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sporco_amd_tvdc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        check(self._lib.sporco_amd_tvdc_sync(self._h))
+
+    def plan(self):
+        """``dict(V, items, strips, R, nseg, TW, SV, sblocks)``: elements per item, items per row, strips per
+        row, rows per segment, segments, columns a strip covers (the stencil kernels); planes per access and
+        workgroups of ``tvdc_solve``."""
+        out = (ctypes.c_int64 * 8)()
+        check(self._lib.sporco_amd_tvdc_plan(self._h, out))
+        return dict(zip(('V', 'items', 'strips', 'R', 'nseg', 'TW', 'SV', 'sblocks'), (int(v) for v in out)))
+
+    def var_shape(self, var):
+        return ((self.blocks,) if var in (TVDC_Y, TVDC_U) else ()) + self.dims
+
+    def upload(self, var, a):
+        """``a``: a host array, a device pointer (int) of an array of the variable's size, or None
+        (a weight goes back to its scalar)."""
+        if a is None:
+            check(self._lib.sporco_amd_tvdc_upload(self._h, int(var), None, 0))
+        elif isinstance(a, int):
+            check(self._lib.sporco_amd_tvdc_upload(self._h, int(var), ctypes.c_void_p(a), 1))
+        else:
+            a = _carr(a, self.dtype)
+            if a.size != int(np.prod(self.var_shape(var))):
+                raise ValueError("array of %d elements for a variable of shape %s" % (a.size, self.var_shape(var)))
+            check(self._lib.sporco_amd_tvdc_upload(self._h, int(var), _ptr(a), 0))
+
+    def download(self, var, dst_ptr=None):
+        """To a new host array, or (``dst_ptr``: device pointer) device to device."""
+        if dst_ptr is not None:
+            check(self._lib.sporco_amd_tvdc_download(self._h, int(var), ctypes.c_void_p(dst_ptr), 1))
+            return None
+        out = np.empty(self.var_shape(var), dtype=self.dtype)
+        check(self._lib.sporco_amd_tvdc_download(self._h, int(var), _ptr(out), 0))
+        return out
+
+    def set_kernel(self, a, ah=None, aw=None):
+        """``a``: a host array of shape (ah, aw, PA), or a device pointer (int) with ``ah``, ``aw`` given."""
+        if isinstance(a, int):
+            check(self._lib.sporco_amd_tvdc_set_kernel(self._h, ctypes.c_void_p(a), int(ah), int(aw), 1))
+        else:
+            a = _carr(a, self.dtype)
+            if a.ndim != 3 or a.shape[2] != self.PA:
+                raise ValueError("the kernel has shape (ah, aw, %d)" % self.PA)
+            check(self._lib.sporco_amd_tvdc_set_kernel(self._h, _ptr(a), a.shape[0], a.shape[1], 0))
+
+    def xstep(self, params):
+        check(self._lib.sporco_amd_tvdc_xstep(self._h, ctypes.byref(params)))
+
+    def ystep(self, params):
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_tvdc_ystep(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def adjoint(self):
+        check(self._lib.sporco_amd_tvdc_adjoint(self._h))
+
+    def profile(self, enable):
+        check(self._lib.sporco_amd_tvdc_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self):
+        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
+        res = {}
+        for slot in range(self._lib.sporco_amd_profile_slots()):
+            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
+            check(self._lib.sporco_amd_tvdc_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
+                                                         ctypes.byref(cnt)))
             if cnt.value:
                 res[name.value.decode()] = (ms.value, cnt.value)
         return res

@@ -973,4 +973,134 @@ int sporco_amd_tvd_profile_read(sporco_amd_tvd_t h, int slot, const char **name,
     SA_API_END
 }
 
+// ---- TVL2Deconv / TVL1Deconv: a handle of its own (csc_impl.h TvdcBase) ---------------------------------
+#define SA_TVDC_HANDLE(h)                                                              \
+    SA_REQUIRE((h) != nullptr && (h)->impl, "null TV deconvolution handle");           \
+    SA_HIP(hipSetDevice((h)->device));
+
+static int tvdc_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int64_t PA, bool l1,
+                       int device, void *stream, sporco_amd_tvdc_t *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out != nullptr, "null argument");
+    SA_REQUIRE(H >= 2 && W >= 2 && P >= 1 && C >= 1, "tvdc: H, W >= 2, P, C >= 1");
+    SA_REQUIRE(PA == P || PA == 1, "tvdc: the kernel has P planes or one");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    std::unique_ptr<sporco_amd_tvdc> h(new sporco_amd_tvdc);
+    h->device = device;
+    h->impl.reset(make_tvdc(dtype, H, W, P, C, vector_tv != 0, l1, PA, device, stream));
+    *out = h.release();
+    SA_API_END
+}
+
+int sporco_amd_tvdc_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int64_t PA,
+                           int device, void *stream, sporco_amd_tvdc_t *out) {
+    return tvdc_create(dtype, H, W, P, C, vector_tv, PA, false, device, stream, out);
+}
+
+int sporco_amd_tvl1dc_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int64_t PA,
+                             int device, void *stream, sporco_amd_tvdc_t *out) {
+    return tvdc_create(dtype, H, W, P, C, vector_tv, PA, true, device, stream, out);
+}
+
+int sporco_amd_tvdc_destroy(sporco_amd_tvdc_t h) {
+    SA_API_BEGIN
+    if (h) {
+        (void)hipSetDevice(h->device);
+        delete h;
+    }
+    SA_API_END
+}
+
+int sporco_amd_tvdc_sync(sporco_amd_tvdc_t h) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    h->impl->sync();
+    SA_API_END
+}
+
+int sporco_amd_tvdc_plan(sporco_amd_tvdc_t h, int64_t out[8]) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    h->impl->plan(out);
+    SA_API_END
+}
+
+int sporco_amd_tvdc_upload(sporco_amd_tvdc_t h, int var, const void *src, int on_device) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    h->impl->upload(var, src, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_tvdc_download(sporco_amd_tvdc_t h, int var, void *dst, int on_device) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    h->impl->download(var, dst, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_tvdc_set_kernel(sporco_amd_tvdc_t h, const void *A, int32_t ah, int32_t aw, int on_device) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    h->impl->set_kernel(A, ah, aw, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_tvdc_xstep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    SA_REQUIRE(p != nullptr, "null argument");
+    h->impl->xstep(*p);
+    SA_API_END
+}
+
+int sporco_amd_tvdc_ystep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
+    h->impl->ystep(*p, out);
+    SA_API_END
+}
+
+int sporco_amd_tvdc_adjoint(sporco_amd_tvdc_t h) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    h->impl->adjoint();
+    SA_API_END
+}
+
+int sporco_amd_tvdc_profile(sporco_amd_tvdc_t h, int enable) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    h->impl->sync();
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (enable)
+        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
+            hipEvent_t e;
+            SA_HIP(hipEventCreate(&e));
+            pr.pool.push_back(e);
+        }
+    pr.on = enable != 0;
+    SA_API_END
+}
+
+int sporco_amd_tvdc_profile_read(sporco_amd_tvdc_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
+    SA_API_BEGIN
+    SA_TVDC_HANDLE(h);
+    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (name) *name = kProfNames[slot];
+    if (total_ms) *total_ms = pr.total_ms[slot];
+    if (launches) *launches = pr.count[slot];
+    pr.total_ms[slot] = 0.0;
+    pr.count[slot] = 0;
+    SA_API_END
+}
+
 }  // extern "C"

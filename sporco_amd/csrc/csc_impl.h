@@ -27,6 +27,7 @@
 #include "csc_rtv.h"
 #include "csc_tv.h"
 #include "csc_tvd.h"
+#include "csc_tvdc.h"
 #include "fft.h"
 
 #include <atomic>
@@ -116,6 +117,12 @@ enum ProfSlot {
     PS_TVD_ADJOINT,             // ... A^T (Y - U), A^T U and the dual-residual sums
     PS_TVL1_YSTEP,              // TVL1Denoise: relax + y step + u step of the three blocks + the sums that need X
     PS_TVL1_ADJOINT,            // ... A^T (Y - U), A^T U with the identity block, || A^T U ||^2 and || U ||^2
+    PS_TVDC_RFFT2,              // TVL2Deconv / TVL1Deconv: the forward transform pair of the right-hand side (csc_tvdc.h)
+    PS_TVDC_SOLVE,              // ... the pointwise x step solve with its by-products
+    PS_TVDC_IRFFT2,             // ... the inverse transform pair: X (l1: X and H X)
+    PS_TVDC_YSTEP,              // ... periodic gradient + relax + y step + u step + sums
+    PS_TVDC_ADJOINT,            // ... G^T Y, G^T U (l1: with the data blocks beside them) and the l2 dual-residual sums
+    PS_TVDC_DUAL,               // ... l1: the transform of (G^T U_g, U_d) and the norm of A^T U over spectra
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -328,6 +335,23 @@ struct TvdBase {
 };
 TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, bool l1, int device, void *stream);
 
+// The handle of TVL2Deconv and, in its l1 mode, TVL1Deconv (api_tvdc.inc): the arrays and spectra of one
+// (H, W, P) problem, the transform plans of H and W and a stream.
+struct TvdcBase {
+    virtual ~TvdcBase() {}
+    virtual void sync() = 0;
+    virtual void plan(int64_t out[8]) = 0;
+    virtual void upload(int var, const void *src, bool on_device) = 0;
+    virtual void download(int var, void *dst, bool on_device) = 0;
+    virtual void set_kernel(const void *src, int ah, int aw, bool on_device) = 0;
+    virtual void xstep(const sporco_amd_tvdc_params &p) = 0;
+    virtual void ystep(const sporco_amd_tvdc_params &p, double *out_host) = 0;
+    virtual void adjoint() = 0;
+    Profiler prof;
+};
+TvdcBase *make_tvdc(int dtype, int H, int W, int64_t P, int C, bool vector_tv, bool l1, int64_t PA, int device,
+                    void *stream);
+
 // the one place that instantiates Csc<float> / Csc<double> (csc_api.hip)
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream,
                   int depth = 1);
@@ -347,6 +371,11 @@ struct sporco_amd_csc {
 
 struct sporco_amd_tvd {
     std::unique_ptr<sporco_amd::TvdBase> impl;
+    int device;
+};
+
+struct sporco_amd_tvdc {
+    std::unique_ptr<sporco_amd::TvdcBase> impl;
     int device;
 };
 

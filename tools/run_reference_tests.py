@@ -4,7 +4,9 @@ it): run the unmodified reference's OWN test files for the hot-path modules with
 ``sporco.admm.cbpdn`` etc. replaced by the modules of this package, on the CPU simulator build,
 and report per test whether it passes.  A failure inside a class that SURVEY.md section 8 puts in
 scope is a gap to close; classes outside it (ConvElasticNet, ConvTwoBlockCnstrnt, ...) are
-expected to be missing.
+expected to be missing.  A test that ends in this package's NotImplementedError is a refusal, not a gap:
+in admm/test_tvl1.py and admm/test_tvl2.py those are the complex-valued cases, the three-axis volumes and (a
+TypeError) the float16 case: 10 of 32; every other Denoise and Deconv test there passes against this package.
 
     python tools/run_reference_tests.py [pytest args]
 """
@@ -32,10 +34,12 @@ ALIASES = {
     'sporco.pgm.backtrack': 'sporco_amd.pgm.backtrack',
     'sporco.pgm.stepsize': 'sporco_amd.pgm.stepsize',
     'sporco.pgm.momentum': 'sporco_amd.pgm.momentum',
+    'sporco.admm.tvl1': 'sporco_amd.admm.tvl1',
+    'sporco.admm.tvl2': 'sporco_amd.admm.tvl2',
 }
 FILES = ['admm/test_cbpdn.py', 'admm/test_ccmod.py', 'admm/test_ccmodmd.py', 'pgm/test_cbpdn.py',
          'pgm/test_ccmod.py', 'dictlrn/test_cbpdndl.py', 'dictlrn/test_cbpdndlmd.py',
-         'dictlrn/test_onlinecdl.py']
+         'dictlrn/test_onlinecdl.py', 'admm/test_tvl1.py', 'admm/test_tvl2.py']
 
 
 def main():
@@ -44,6 +48,15 @@ def main():
     from conftest import use_backend
     use_backend('hostsim')
     import sporco  # noqa: F401  (the reference package: everything not aliased comes from it)
+    try:
+        import past.utils  # noqa: F401  (the reference's test_tvl1.py / test_tvl2.py import old_div from it)
+    except ImportError:
+        import numbers
+        import types
+        past, utils = types.ModuleType('past'), types.ModuleType('past.utils')
+        utils.old_div = lambda a, b: a // b if isinstance(a, numbers.Integral) and isinstance(b, numbers.Integral) else a / b
+        past.utils = utils
+        sys.modules['past'], sys.modules['past.utils'] = past, utils
     if any(a.endswith('test_prox.py') for a in sys.argv[1:]):
         # (the reference's tests/test_prox.py against this package's prox module: what it lacks fails)
         ALIASES['sporco.prox'] = 'sporco_amd.prox'
