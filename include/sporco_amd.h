@@ -1192,6 +1192,60 @@ int sporco_amd_tvdc_profile(sporco_amd_tvdc_t h, int enable);
 int sporco_amd_tvdc_profile_read(sporco_amd_tvdc_t h, int slot, const char **name, double *total_ms,
                                  int64_t *count);
 
+/* ---- l1-spline fit: sporco.admm.spline.SplineL1 (sporco/admm/spline.py:24-291) and the orthonormal DCT-II
+ * of sporco.fft.dctii / idctii (sporco/fft.py:318-372) --------------------------------------------------
+ *     minimise ||Wdf (x - s)||_1 + (lmbda / 2) ||D x||^2      on  x - y = s,
+ * D the second difference with reflecting ends, diagonal under the DCT-II with eigenvalues
+ * alpha[k1, k2] = (-2 + 2 cos(pi k1 / H)) + (-2 + 2 cos(pi k2 / W)).  The x step is
+ * X = idct(Gamma dct(Y + S - U)), Gamma = 1 / (1 + (lmbda / rho) alpha^2): the DCT is computed through ONE
+ * real transform of the same size on a permuted array (rfft2 / irfft2 on the generic chain) with a
+ * pointwise twiddle kernel between the two (csrc/csc_spline.h).  The handle owns S, X, Y, U, the permuted
+ * right-hand side arrays, the work spectrum and the transform plans of H and W; a transform length that
+ * does not fit is refused at creation ("transform length too large").  A 1-D signal of N samples is served
+ * as H = 1, W = N.  Y, U start at zero. */
+typedef struct sporco_amd_spl *sporco_amd_spl_t;
+#define SPORCO_AMD_SPL_S 0    /* real (H,W,P)  the signal                                               */
+#define SPORCO_AMD_SPL_X 1    /* real (H,W,P)  the result of the x step (download only)                 */
+#define SPORCO_AMD_SPL_Y 2    /* real (H,W,P)                                                           */
+#define SPORCO_AMD_SPL_U 3    /* real (H,W,P)  (without a pending u_scale)                              */
+#define SPORCO_AMD_SPL_WDF 4  /* real (H,W,P)  DFidWeight array (upload NULL: the scalar wdf)           */
+typedef struct {
+    double rho, lmbda, rlx;
+    double u_scale;           /* pending U /= rsf (admm.py:573): the x and y steps apply it                 */
+    double wdf;               /* scalar DFidWeight, read where no array is set                              */
+    int32_t geval_y;          /* DFid at Y, else at X - S                                                   */
+    int32_t lin_solve_check;  /* the x step also forms OUT_XRRS_*                                           */
+    int32_t want_stats;       /* the x step also forms OUT_RGR                                              */
+    int32_t reserved;
+} sporco_amd_spl_params;
+int sporco_amd_spl_create(int dtype, int32_t H, int32_t W, int64_t P, int device, void *stream, sporco_amd_spl_t *out);
+int sporco_amd_spl_destroy(sporco_amd_spl_t h);
+int sporco_amd_spl_sync(sporco_amd_spl_t h);
+/* The launch plan: out[0] = planes per access (2: 16 bytes of spectrum in float32), out[1] = row pairs
+ * {k1, H - k1} of spl_solve, out[2] = its workgroups, out[3] = the workgroups of spl_ystep. */
+int sporco_amd_spl_plan(sporco_amd_spl_t h, int64_t out[4]);
+/* Copy an array in or out; on_device: src / dst is a device pointer (no host traffic).  Uploading S also
+ * forms ||S||^2; uploading S, Y or U also forms the permuted arrays of the next x step. */
+int sporco_amd_spl_upload(sporco_amd_spl_t h, int var, const void *src, int on_device);
+int sporco_amd_spl_download(sporco_amd_spl_t h, int var, void *dst, int on_device);
+/* The x step: X = idct(Gamma dct(Y + S - u_scale U)), kept in the transform's permuted order. */
+int sporco_amd_spl_xstep(sporco_amd_spl_t h, const sporco_amd_spl_params *p);
+/* relax_AX + ystep + ustep and the arrays of the next x step in one launch, one reduction, one host read.
+ * out: OUT_R2 = ||X - Y - S||^2, OUT_AX2 = ||X||^2, OUT_Y2, OUT_S2 = ||Y - Yprev||^2 (rho applied by the
+ * host), OUT_U2 = ||U||^2, OUT_DFID = sum |Wdf g|, OUT_C2 = ||S||^2; from the x step, with want_stats:
+ * OUT_RGR = sum (alpha Xhat)^2 (twice Reg), with lin_solve_check: OUT_XRRS_*.  U is stored with u_scale
+ * applied: the pending factor is 1 afterwards. */
+int sporco_amd_spl_ystep(sporco_amd_spl_t h, const sporco_amd_spl_params *p, double out[SPORCO_AMD_OUT_COUNT]);
+/* Per-kernel event timing of the handle's launches, as sporco_amd_csc_profile / _profile_read. */
+int sporco_amd_spl_profile(sporco_amd_spl_t h, int enable);
+int sporco_amd_spl_profile_read(sporco_amd_spl_t h, int slot, const char **name, double *total_ms,
+                                int64_t *count);
+/* out(H, W, P) = the orthonormal DCT-II (idctii: its inverse) of in(H, W, P) over axes (0, 1), H >= 1,
+ * W >= 2; on_device: both pointers are device pointers.  in != out.  Stateless: each call allocates its work
+ * arrays and transform plans on the current device, runs on the null stream and synchronises the device. */
+int sporco_amd_dctii(int dtype, int32_t H, int32_t W, int64_t P, const void *in, void *out, int on_device);
+int sporco_amd_idctii(int dtype, int32_t H, int32_t W, int64_t P, const void *in, void *out, int on_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,9 @@ EXPORTS = (
     'sporco_amd_tvdc_plan', 'sporco_amd_tvdc_upload', 'sporco_amd_tvdc_download', 'sporco_amd_tvdc_set_kernel',
     'sporco_amd_tvdc_xstep', 'sporco_amd_tvdc_ystep', 'sporco_amd_tvdc_adjoint', 'sporco_amd_tvdc_profile',
     'sporco_amd_tvdc_profile_read',
+    'sporco_amd_spl_create', 'sporco_amd_spl_destroy', 'sporco_amd_spl_sync', 'sporco_amd_spl_plan',
+    'sporco_amd_spl_upload', 'sporco_amd_spl_download', 'sporco_amd_spl_xstep', 'sporco_amd_spl_ystep',
+    'sporco_amd_spl_profile', 'sporco_amd_spl_profile_read', 'sporco_amd_dctii', 'sporco_amd_idctii',
 )
 
 
@@ -189,6 +192,17 @@ class TvdcParams(ctypes.Structure):
 
 
 TVDC_S, TVDC_X, TVDC_Y, TVDC_U, TVDC_WDF, TVDC_WTV, TVDC_HX = range(7)
+
+
+class SplParams(ctypes.Structure):
+    """sporco_amd_spl_params: scalars of one SplineL1 step."""
+    _fields_ = [('rho', ctypes.c_double), ('lmbda', ctypes.c_double), ('rlx', ctypes.c_double),
+                ('u_scale', ctypes.c_double), ('wdf', ctypes.c_double),
+                ('geval_y', ctypes.c_int32), ('lin_solve_check', ctypes.c_int32), ('want_stats', ctypes.c_int32),
+                ('reserved', ctypes.c_int32)]
+
+
+SPL_S, SPL_X, SPL_Y, SPL_U, SPL_WDF = range(5)
 
 REDUCE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
 EUNSUPPORTED = -5
@@ -420,6 +434,18 @@ def load(path=None):
                                          ctypes.POINTER(ctypes.c_int64)],
         'sporco_amd_tvd_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                         ctypes.POINTER(i64)],
+        'sporco_amd_spl_create': [ctypes.c_int, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_spl_destroy': [vp], 'sporco_amd_spl_sync': [vp],
+        'sporco_amd_spl_plan': [vp, ctypes.POINTER(i64)],
+        'sporco_amd_spl_upload': [vp, ctypes.c_int, vp, ctypes.c_int],
+        'sporco_amd_spl_download': [vp, ctypes.c_int, vp, ctypes.c_int],
+        'sporco_amd_spl_xstep': [vp, ctypes.POINTER(SplParams)],
+        'sporco_amd_spl_ystep': [vp, ctypes.POINTER(SplParams), dptr],
+        'sporco_amd_spl_profile': [vp, ctypes.c_int],
+        'sporco_amd_spl_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
+                                        ctypes.POINTER(i64)],
+        'sporco_amd_dctii': [ctypes.c_int, i32, i32, i64, vp, vp, ctypes.c_int],
+        'sporco_amd_idctii': [ctypes.c_int, i32, i32, i64, vp, vp, ctypes.c_int],
     }
     for name, argtypes in sig.items():
         getattr(lib, name).argtypes = argtypes
@@ -1357,3 +1383,100 @@ class TvdcHandle(object):
             if cnt.value:
                 res[name.value.decode()] = (ms.value, cnt.value)
         return res
+
+
+class SplHandle(object):
+    """Owner of one device-side SplineL1 problem (sporco_amd_spl_*).  Arrays of shape (H, W, P); a 1-D
+    signal of N samples is H = 1, W = N."""
+
+    def __init__(self, H, W, P, dtype, device=0, stream=None):
+        self.dims = (int(H), int(W), int(P))
+        self.dtype = np.dtype(dtype)
+        h = ctypes.c_void_p()
+        check(lib().sporco_amd_spl_create(dtype_code(dtype), int(H), int(W), int(P), int(device),
+                                          ctypes.c_void_p(stream or 0), ctypes.byref(h)))
+        self._h = h
+        self._lib = lib()
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sporco_amd_spl_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        check(self._lib.sporco_amd_spl_sync(self._h))
+
+    def plan(self):
+        """``dict(V, pairs, sblocks, yblocks)``: planes per access, the row pairs {k1, H - k1} of ``spl_solve``,
+        its workgroups and those of ``spl_ystep``."""
+        out = (ctypes.c_int64 * 4)()
+        check(self._lib.sporco_amd_spl_plan(self._h, out))
+        return dict(zip(('V', 'pairs', 'sblocks', 'yblocks'), (int(v) for v in out)))
+
+    def upload(self, var, a):
+        """``a``: a host array, a device pointer (int) of an array of the variable's size, or None
+        (the weight goes back to its scalar)."""
+        if a is None:
+            check(self._lib.sporco_amd_spl_upload(self._h, int(var), None, 0))
+        elif isinstance(a, int):
+            check(self._lib.sporco_amd_spl_upload(self._h, int(var), ctypes.c_void_p(a), 1))
+        else:
+            a = _carr(a, self.dtype)
+            if a.size != int(np.prod(self.dims)):
+                raise ValueError("array of %d elements for a variable of shape %s" % (a.size, self.dims))
+            check(self._lib.sporco_amd_spl_upload(self._h, int(var), _ptr(a), 0))
+
+    def download(self, var, dst_ptr=None):
+        """To a new host array, or (``dst_ptr``: device pointer) device to device."""
+        if dst_ptr is not None:
+            check(self._lib.sporco_amd_spl_download(self._h, int(var), ctypes.c_void_p(dst_ptr), 1))
+            return None
+        out = np.empty(self.dims, dtype=self.dtype)
+        check(self._lib.sporco_amd_spl_download(self._h, int(var), _ptr(out), 0))
+        return out
+
+    def xstep(self, params):
+        check(self._lib.sporco_amd_spl_xstep(self._h, ctypes.byref(params)))
+
+    def ystep(self, params):
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_spl_ystep(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def profile(self, enable):
+        check(self._lib.sporco_amd_spl_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self):
+        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
+        res = {}
+        for slot in range(self._lib.sporco_amd_profile_slots()):
+            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
+            check(self._lib.sporco_amd_spl_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
+                                                        ctypes.byref(cnt)))
+            if cnt.value:
+                res[name.value.decode()] = (ms.value, cnt.value)
+        return res
+
+
+def dct2(a, out=None, inverse=False):
+    """The orthonormal DCT-II (``inverse``: its inverse) over axes (0, 1) of a C-ordered (H, W, ...) array,
+    H >= 1, W >= 2: a host array to a new host array, or a :class:`sporco_amd.device.DeviceArray` to ``out``
+    (a DeviceArray of the same shape and dtype, every element of which is written exactly once)."""
+    fn = lib().sporco_amd_idctii if inverse else lib().sporco_amd_dctii
+    H, W = int(a.shape[0]), int(a.shape[1])
+    P = int(np.prod(a.shape[2:])) if len(a.shape) > 2 else 1
+    if isinstance(a, np.ndarray):
+        a = _carr(a, a.dtype)
+        res = np.empty(a.shape, dtype=a.dtype)
+        check(fn(dtype_code(a.dtype), H, W, P, _ptr(a), _ptr(res), 0))
+        return res
+    if out is None or tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or out.ptr == a.ptr:
+        raise ValueError("a device array is transformed into another of the same shape and dtype")
+    check(fn(dtype_code(a.dtype), H, W, P, ctypes.c_void_p(a.ptr), ctypes.c_void_p(out.ptr), 1))
+    return out

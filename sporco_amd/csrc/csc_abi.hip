@@ -1103,4 +1103,126 @@ int sporco_amd_tvdc_profile_read(sporco_amd_tvdc_t h, int slot, const char **nam
     SA_API_END
 }
 
+// ---- SplineL1: a handle of its own (csc_impl.h SplBase), and the stateless DCT ----------------------------
+#define SA_SPL_HANDLE(h)                                                               \
+    SA_REQUIRE((h) != nullptr && (h)->impl, "null spline handle");                     \
+    SA_HIP(hipSetDevice((h)->device));
+
+int sporco_amd_spl_create(int dtype, int32_t H, int32_t W, int64_t P, int device, void *stream, sporco_amd_spl_t *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out != nullptr, "null argument");
+    SA_REQUIRE(H >= 1 && W >= 2 && P >= 1, "spline: H >= 1, W >= 2, P >= 1");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    std::unique_ptr<sporco_amd_spl> h(new sporco_amd_spl);
+    h->device = device;
+    h->impl.reset(make_spl(dtype, H, W, P, device, stream));
+    *out = h.release();
+    SA_API_END
+}
+
+int sporco_amd_spl_destroy(sporco_amd_spl_t h) {
+    SA_API_BEGIN
+    if (h) {
+        (void)hipSetDevice(h->device);
+        delete h;
+    }
+    SA_API_END
+}
+
+int sporco_amd_spl_sync(sporco_amd_spl_t h) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    h->impl->sync();
+    SA_API_END
+}
+
+int sporco_amd_spl_plan(sporco_amd_spl_t h, int64_t out[4]) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    h->impl->plan(out);
+    SA_API_END
+}
+
+int sporco_amd_spl_upload(sporco_amd_spl_t h, int var, const void *src, int on_device) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    h->impl->upload(var, src, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_spl_download(sporco_amd_spl_t h, int var, void *dst, int on_device) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    h->impl->download(var, dst, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_spl_xstep(sporco_amd_spl_t h, const sporco_amd_spl_params *p) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    SA_REQUIRE(p != nullptr, "null argument");
+    h->impl->xstep(*p);
+    SA_API_END
+}
+
+int sporco_amd_spl_ystep(sporco_amd_spl_t h, const sporco_amd_spl_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
+    h->impl->ystep(*p, out);
+    SA_API_END
+}
+
+int sporco_amd_spl_profile(sporco_amd_spl_t h, int enable) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    h->impl->sync();
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (enable)
+        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
+            hipEvent_t e;
+            SA_HIP(hipEventCreate(&e));
+            pr.pool.push_back(e);
+        }
+    pr.on = enable != 0;
+    SA_API_END
+}
+
+int sporco_amd_spl_profile_read(sporco_amd_spl_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
+    SA_API_BEGIN
+    SA_SPL_HANDLE(h);
+    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (name) *name = kProfNames[slot];
+    if (total_ms) *total_ms = pr.total_ms[slot];
+    if (launches) *launches = pr.count[slot];
+    pr.total_ms[slot] = 0.0;
+    pr.count[slot] = 0;
+    SA_API_END
+}
+
+static int spl_dct_api(int dtype, int32_t H, int32_t W, int64_t P, const void *in, void *out, bool inverse, int on_device) {
+    SA_API_BEGIN
+    SA_REQUIRE(in && out && in != out && H >= 1 && W >= 2 && P >= 1, "dctii: bad argument");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    spl_dct_dispatch(dtype, H, W, P, in, out, inverse, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_dctii(int dtype, int32_t H, int32_t W, int64_t P, const void *in, void *out, int on_device) {
+    return spl_dct_api(dtype, H, W, P, in, out, false, on_device);
+}
+
+int sporco_amd_idctii(int dtype, int32_t H, int32_t W, int64_t P, const void *in, void *out, int on_device) {
+    return spl_dct_api(dtype, H, W, P, in, out, true, on_device);
+}
+
 }  // extern "C"

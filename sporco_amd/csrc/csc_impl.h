@@ -28,6 +28,7 @@
 #include "csc_tv.h"
 #include "csc_tvd.h"
 #include "csc_tvdc.h"
+#include "csc_spline.h"
 #include "fft.h"
 
 #include <atomic>
@@ -123,6 +124,10 @@ enum ProfSlot {
     PS_TVDC_YSTEP,              // ... periodic gradient + relax + y step + u step + sums
     PS_TVDC_ADJOINT,            // ... G^T Y, G^T U (l1: with the data blocks beside them) and the l2 dual-residual sums
     PS_TVDC_DUAL,               // ... l1: the transform of (G^T U_g, U_d) and the norm of A^T U over spectra
+    PS_SPL_RFFT2,               // SplineL1: the forward transform pair of the permuted right-hand side (csc_spline.h)
+    PS_SPL_SOLVE,               // ... post-twiddle, Gamma, pre-twiddle in place, Reg and the LinSolveCheck sums
+    PS_SPL_IRFFT2,              // ... the inverse transform pair: X in permuted order
+    PS_SPL_YSTEP,               // ... relax + y step + u step + sums + the permuted arrays of the next x step
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -352,6 +357,22 @@ struct TvdcBase {
 TvdcBase *make_tvdc(int dtype, int H, int W, int64_t P, int C, bool vector_tv, bool l1, int64_t PA, int device,
                     void *stream);
 
+// The handle of SplineL1 (api_spline.inc): the arrays of one (H, W, P) problem, the work spectrum, the DCT's
+// tables, the transform plans of H and W and a stream.
+struct SplBase {
+    virtual ~SplBase() {}
+    virtual void sync() = 0;
+    virtual void plan(int64_t out[4]) = 0;
+    virtual void upload(int var, const void *src, bool on_device) = 0;
+    virtual void download(int var, void *dst, bool on_device) = 0;
+    virtual void xstep(const sporco_amd_spl_params &p) = 0;
+    virtual void ystep(const sporco_amd_spl_params &p, double *out_host) = 0;
+    Profiler prof;
+};
+SplBase *make_spl(int dtype, int H, int W, int64_t P, int device, void *stream);
+// the stateless orthonormal DCT-II (inverse: its inverse) over axes (0, 1) of an (H, W, P) array
+void spl_dct_dispatch(int dtype, int H, int W, int64_t P, const void *in, void *out, bool inverse, bool on_device);
+
 // the one place that instantiates Csc<float> / Csc<double> (csc_api.hip)
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream,
                   int depth = 1);
@@ -376,6 +397,11 @@ struct sporco_amd_tvd {
 
 struct sporco_amd_tvdc {
     std::unique_ptr<sporco_amd::TvdcBase> impl;
+    int device;
+};
+
+struct sporco_amd_spl {
+    std::unique_ptr<sporco_amd::SplBase> impl;
     int device;
 };
 

@@ -167,3 +167,64 @@ def fftconv(a, b, axes=(0, 1), origin=None):
         _lib.dtype_code(dt), ash[0], ash[1], da, vp(ad.ptr), bsh[0], bsh[1], db, vp(bd.ptr),
         og[0], og[1], vp(out.ptr)))
     return out if dev else out.get()
+
+
+def _dct(x, axes, inverse, name):
+    from .device import DeviceArray
+    dev = isinstance(x, DeviceArray)
+    if not dev:
+        x = np.asarray(x)
+        if np.iscomplexobj(x):
+            raise NotImplementedError("sporco_amd.fft.%s handles real-valued arrays" % name)
+    if x.dtype not in (np.float32, np.float64):
+        raise NotImplementedError("sporco_amd.fft.%s works in float32 or float64, not %s" % (name, x.dtype))
+    nd = len(x.shape)
+    if axes is None:
+        if nd not in (1, 2):
+            raise NotImplementedError("sporco_amd.fft.%s: axes=None on arrays of at most two axes" % name)
+        axes = tuple(range(nd))
+    if np.ndim(axes) == 0:
+        axes = (int(axes),)
+    ax = tuple(int(a) + nd if int(a) < 0 else int(a) for a in axes)
+    if len(ax) not in (1, 2) or len(set(ax)) != len(ax) or not all(0 <= a < nd for a in ax):
+        raise NotImplementedError("sporco_amd.fft.%s transforms one or two distinct axes (got %r for %d "
+                                  "dimensions)" % (name, axes, nd))
+    # (the orthonormal transform of an axis of one sample is the identity)
+    ax = tuple(a for a in ax if x.shape[a] > 1)
+    if dev:
+        # device arrays are C-ordered and stay where they are: the transform axes lead, unit axes aside (an axis of
+        # one sample takes no place in memory)
+        keep = [a for a in range(nd) if x.shape[a] > 1]
+        if [keep.index(a) for a in sorted(ax)] != list(range(len(ax))):
+            raise NotImplementedError("sporco_amd.fft.%s: the transform axes of a DeviceArray are its leading ones"
+                                      % name)
+        out = DeviceArray(x.shape, x.dtype)
+        if not ax:
+            vp = ctypes.c_void_p
+            _lib.check(_lib.lib().sporco_amd_dev_axpby(_lib.dtype_code(x.dtype), x.size, 1.0, vp(x.ptr), 0.0, vp(x.ptr),
+                                                       vp(out.ptr)))
+            return out
+        shp = ((1,) if len(ax) == 1 else ()) + tuple(x.shape[a] for a in keep)
+        _lib.dct2(x.reshape(shp), out.reshape(shp), inverse)
+        return out
+    if not ax:
+        return x.copy()
+    # the transform axes to the front (a single axis behind a unit one), transform, and back
+    if len(ax) == 1:
+        m = np.ascontiguousarray(np.moveaxis(x, ax[0], 0)[np.newaxis])
+        return np.ascontiguousarray(np.moveaxis(_lib.dct2(m, inverse=inverse)[0], 0, ax[0]))
+    m = np.ascontiguousarray(np.moveaxis(x, ax, (0, 1)))
+    return np.ascontiguousarray(np.moveaxis(_lib.dct2(m, inverse=inverse), (0, 1), ax))
+
+
+def dctii(x, axes=None):
+    """Orthonormal DCT-II over one or two ``axes`` (sporco/fft.py:318-343), through one real transform of the
+    same size on the device (csrc/csc_spline.h).  Real float32 / float64; ``axes=None``: every axis of an
+    array of at most two.  A NumPy array gives a NumPy array; a
+    :class:`sporco_amd.device.DeviceArray` (transform axes leading) gives a DeviceArray."""
+    return _dct(x, axes, False, 'dctii')
+
+
+def idctii(x, axes=None):
+    """Inverse of :func:`dctii` (sporco/fft.py:347-372)."""
+    return _dct(x, axes, True, 'idctii')
