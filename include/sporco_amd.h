@@ -42,6 +42,8 @@
  *   SPORCO_AMD_MD_GENERIC=1     ConvBPDNMaskDcpl on the generic chain
  *   SPORCO_AMD_CNS_GENERIC=1    consensus dictionary update on the generic chain
  *   SPORCO_AMD_PDL1_GENERIC=1   (tests) pdl1_solve in its one-thread-per-system form on every shape
+ *   SPORCO_AMD_BPDN_PLAIN=1     (tests, measurements) the float32 products of the bpdn handle as fused
+ *                               multiply-add chains instead of the matrix instruction; same bits
  *   SPORCO_AMD_CG_HOST=1        CG dictionary update: the scalars read back every iteration
  *   SPORCO_AMD_PLACEMENT=0|force   no placement search for concurrently written arrays / the search
  *                               (and the striped column output) also for small arrays -- tests
@@ -1245,6 +1247,56 @@ int sporco_amd_spl_profile_read(sporco_amd_spl_t h, int slot, const char **name,
  * arrays and transform plans on the current device, runs on the null stream and synchronises the device. */
 int sporco_amd_dctii(int dtype, int32_t H, int32_t W, int64_t P, const void *in, void *out, int on_device);
 int sporco_amd_idctii(int dtype, int32_t H, int32_t W, int64_t P, const void *in, void *out, int on_device);
+
+/* ---- dense sparse coding: sporco.admm.bpdn BPDN / BPDNJoint / ElasticNet (sporco/admm/bpdn.py:24-748) ----
+ *     minimise (1/2) ||D x - s||^2 + lmbda ||wl1 x||_1 [+ mu ||x||_{2,1}] [+ (mu / 2) ||x||^2]   on  x = y,
+ * D (N, M), S (N, K), X / Y / U (M, K), every array row-major as NumPy has it.  The x step is X = P B with
+ * B = D^T S + rho (Y - U) and the solve matrix P = (D^T D + c I)^-1, c = rho (ElasticNet: mu + rho), which the
+ * caller forms and sets again whenever c or D changes.  One call does an iteration (csrc/csc_bpdn.h); the
+ * products run on the float32 matrix instruction (float64, or SPORCO_AMD_BPDN_PLAIN: as fma chains with the
+ * same bits).  Y and U start at zero. */
+typedef struct sporco_amd_bpdn *sporco_amd_bpdn_t;
+#define SPORCO_AMD_BPDN_MAX_DIM 512 /* the largest N and M */
+#define SPORCO_AMD_BPDN_S 0    /* (N,K)  the signals; setting it (or the dictionary) forms D^T S on the device */
+#define SPORCO_AMD_BPDN_X 1    /* (M,K)  the result of the x step (download only)                            */
+#define SPORCO_AMD_BPDN_Y 2    /* (M,K)                                                                      */
+#define SPORCO_AMD_BPDN_U 3    /* (M,K)  (without a pending u_scale)                                         */
+#define SPORCO_AMD_BPDN_WL1 4  /* (M,K)  L1Weight array (upload NULL: the scalar wl1)                        */
+#define SPORCO_AMD_BPDN_DTS 5  /* (M,K)  D^T S (download only)                                               */
+typedef struct {
+    double rho, lmbda, mu, rlx;
+    double u_scale;           /* pending U /= rsf (admm.py:573): the iteration applies it                   */
+    double wl1;               /* scalar L1Weight, read where no array is set                                */
+    double c;                 /* the c of the solve matrix in use (LinSolveCheck)                           */
+    int32_t nonneg;           /* NonNegCoef                                                                 */
+    int32_t feval_x;          /* DFid at X, else at Y                                                       */
+    int32_t geval_y;          /* the regularisation terms at Y, else at X                                   */
+    int32_t want_x;           /* store X (always stored with joint or lin_solve_check)                      */
+    int32_t joint;            /* BPDNJoint: the l2,1 term with weight mu                                    */
+    int32_t lin_solve_check;  /* also form OUT_XRRS_*                                                       */
+    int32_t reserved[2];
+} sporco_amd_bpdn_params;
+int sporco_amd_bpdn_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_bpdn_t *out);
+int sporco_amd_bpdn_destroy(sporco_amd_bpdn_t h);
+int sporco_amd_bpdn_sync(sporco_amd_bpdn_t h);
+/* out[0] = columns of a workgroup's block, out[1] = workgroups, out[2] = 1 where the products use the matrix
+ * instruction, out[3] = bytes of LDS of a workgroup. */
+int sporco_amd_bpdn_plan(sporco_amd_bpdn_t h, int64_t out[4]);
+/* D: host (N, M) in the handle's precision; P: host (M, M).  Y and U are kept. */
+int sporco_amd_bpdn_set_dict(sporco_amd_bpdn_t h, const void *D);
+int sporco_amd_bpdn_set_solve(sporco_amd_bpdn_t h, const void *P);
+/* Copy a host array in or out.  X and D^T S are results: an upload of either only prefills the array (tests). */
+int sporco_amd_bpdn_upload(sporco_amd_bpdn_t h, int var, const void *src);
+int sporco_amd_bpdn_download(sporco_amd_bpdn_t h, int var, void *dst);
+/* One iteration: x step, relax_AX, y step, u step, one reduction, one host read.  out: OUT_R2 = ||X - Y||^2,
+ * OUT_AX2 = ||X||^2, OUT_Y2, OUT_S2 = ||Y - Yprev||^2 (rho applied by the host), OUT_U2, OUT_DFID =
+ * ||D g - S||^2 (the host halves it), OUT_L1 = sum |wl1 g|, joint: OUT_L21 = sum_m ||g_m||, with
+ * lin_solve_check: OUT_XRRS_*.  U is stored with u_scale applied: the pending factor is 1 afterwards. */
+int sporco_amd_bpdn_iter(sporco_amd_bpdn_t h, const sporco_amd_bpdn_params *p, double out[SPORCO_AMD_OUT_COUNT]);
+/* Per-kernel event timing of the handle's launches, as sporco_amd_csc_profile / _profile_read. */
+int sporco_amd_bpdn_profile(sporco_amd_bpdn_t h, int enable);
+int sporco_amd_bpdn_profile_read(sporco_amd_bpdn_t h, int slot, const char **name, double *total_ms,
+                                 int64_t *count);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,9 @@ EXPORTS = (
     'sporco_amd_spl_create', 'sporco_amd_spl_destroy', 'sporco_amd_spl_sync', 'sporco_amd_spl_plan',
     'sporco_amd_spl_upload', 'sporco_amd_spl_download', 'sporco_amd_spl_xstep', 'sporco_amd_spl_ystep',
     'sporco_amd_spl_profile', 'sporco_amd_spl_profile_read', 'sporco_amd_dctii', 'sporco_amd_idctii',
+    'sporco_amd_bpdn_create', 'sporco_amd_bpdn_destroy', 'sporco_amd_bpdn_sync', 'sporco_amd_bpdn_plan',
+    'sporco_amd_bpdn_set_dict', 'sporco_amd_bpdn_set_solve', 'sporco_amd_bpdn_upload', 'sporco_amd_bpdn_download',
+    'sporco_amd_bpdn_iter', 'sporco_amd_bpdn_profile', 'sporco_amd_bpdn_profile_read',
 )
 
 
@@ -203,6 +206,20 @@ class SplParams(ctypes.Structure):
 
 
 SPL_S, SPL_X, SPL_Y, SPL_U, SPL_WDF = range(5)
+
+
+class BpdnParams(ctypes.Structure):
+    """sporco_amd_bpdn_params: scalars of one BPDN / BPDNJoint / ElasticNet iteration."""
+    _fields_ = [('rho', ctypes.c_double), ('lmbda', ctypes.c_double), ('mu', ctypes.c_double),
+                ('rlx', ctypes.c_double), ('u_scale', ctypes.c_double), ('wl1', ctypes.c_double),
+                ('c', ctypes.c_double),
+                ('nonneg', ctypes.c_int32), ('feval_x', ctypes.c_int32), ('geval_y', ctypes.c_int32),
+                ('want_x', ctypes.c_int32), ('joint', ctypes.c_int32), ('lin_solve_check', ctypes.c_int32),
+                ('reserved', ctypes.c_int32 * 2)]
+
+
+BPDN_S, BPDN_X, BPDN_Y, BPDN_U, BPDN_WL1, BPDN_DTS = range(6)
+BPDN_MAX_DIM = 512
 
 REDUCE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
 EUNSUPPORTED = -5
@@ -442,6 +459,16 @@ def load(path=None):
         'sporco_amd_spl_xstep': [vp, ctypes.POINTER(SplParams)],
         'sporco_amd_spl_ystep': [vp, ctypes.POINTER(SplParams), dptr],
         'sporco_amd_spl_profile': [vp, ctypes.c_int],
+        'sporco_amd_bpdn_create': [ctypes.c_int, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_bpdn_destroy': [vp], 'sporco_amd_bpdn_sync': [vp],
+        'sporco_amd_bpdn_plan': [vp, ctypes.POINTER(i64)],
+        'sporco_amd_bpdn_set_dict': [vp, vp], 'sporco_amd_bpdn_set_solve': [vp, vp],
+        'sporco_amd_bpdn_upload': [vp, ctypes.c_int, vp],
+        'sporco_amd_bpdn_download': [vp, ctypes.c_int, vp],
+        'sporco_amd_bpdn_iter': [vp, ctypes.POINTER(BpdnParams), dptr],
+        'sporco_amd_bpdn_profile': [vp, ctypes.c_int],
+        'sporco_amd_bpdn_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
+                                         ctypes.POINTER(i64)],
         'sporco_amd_spl_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                         ctypes.POINTER(i64)],
         'sporco_amd_dctii': [ctypes.c_int, i32, i32, i64, vp, vp, ctypes.c_int],
@@ -1459,6 +1486,95 @@ class SplHandle(object):
             name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
             check(self._lib.sporco_amd_spl_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
                                                         ctypes.byref(cnt)))
+            if cnt.value:
+                res[name.value.decode()] = (ms.value, cnt.value)
+        return res
+
+
+class BpdnHandle(object):
+    """Owner of one device-side BPDN / BPDNJoint / ElasticNet problem (sporco_amd_bpdn_*): D (N, M), S (N, K),
+    X / Y / U (M, K), host arrays in and out."""
+
+    def __init__(self, N, M, K, dtype, device=0, stream=None):
+        self.dims = (int(N), int(M), int(K))
+        self.dtype = np.dtype(dtype)
+        h = ctypes.c_void_p()
+        check(lib().sporco_amd_bpdn_create(dtype_code(dtype), int(N), int(M), int(K), int(device),
+                                           ctypes.c_void_p(stream or 0), ctypes.byref(h)))
+        self._h = h
+        self._lib = lib()
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sporco_amd_bpdn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        check(self._lib.sporco_amd_bpdn_sync(self._h))
+
+    def plan(self):
+        """``dict(KB, blocks, mfma, lds)``: the columns of a workgroup's block, the workgroups, whether the
+        products use the matrix instruction, the bytes of LDS of a workgroup."""
+        out = (ctypes.c_int64 * 4)()
+        check(self._lib.sporco_amd_bpdn_plan(self._h, out))
+        return dict(zip(('KB', 'blocks', 'mfma', 'lds'), (int(v) for v in out)))
+
+    def _shape(self, var):
+        N, M, K = self.dims
+        return (N, K) if var == BPDN_S else (M, K)
+
+    def set_dict(self, D):
+        D = _carr(D, self.dtype)
+        if D.shape != self.dims[:2]:
+            raise ValueError("dictionary of shape %s where %s is expected" % (D.shape, self.dims[:2]))
+        check(self._lib.sporco_amd_bpdn_set_dict(self._h, _ptr(D)))
+
+    def set_solve(self, P):
+        P = _carr(P, self.dtype)
+        if P.shape != (self.dims[1], self.dims[1]):
+            raise ValueError("solve matrix of shape %s where %s is expected" % (P.shape, (self.dims[1],) * 2))
+        check(self._lib.sporco_amd_bpdn_set_solve(self._h, _ptr(P)))
+
+    def upload(self, var, a):
+        """``a``: a host array of the variable's shape, or None (the weight goes back to its scalar)."""
+        if a is None:
+            check(self._lib.sporco_amd_bpdn_upload(self._h, int(var), None))
+            return
+        a = _carr(a, self.dtype)
+        if a.shape != self._shape(var):
+            raise ValueError("array of shape %s where %s is expected" % (a.shape, self._shape(var)))
+        check(self._lib.sporco_amd_bpdn_upload(self._h, int(var), _ptr(a)))
+
+    def download(self, var, out=None):
+        """To a new host array, or into ``out`` (C-ordered, the variable's shape and the handle's dtype)."""
+        if out is None:
+            out = np.empty(self._shape(var), dtype=self.dtype)
+        elif out.shape != self._shape(var) or out.dtype != self.dtype or not out.flags['C_CONTIGUOUS']:
+            raise ValueError("out does not have the variable's shape and dtype")
+        check(self._lib.sporco_amd_bpdn_download(self._h, int(var), _ptr(out)))
+        return out
+
+    def iter(self, params):
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_bpdn_iter(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def profile(self, enable):
+        check(self._lib.sporco_amd_bpdn_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self):
+        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
+        res = {}
+        for slot in range(self._lib.sporco_amd_profile_slots()):
+            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
+            check(self._lib.sporco_amd_bpdn_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
+                                                         ctypes.byref(cnt)))
             if cnt.value:
                 res[name.value.decode()] = (ms.value, cnt.value)
         return res

@@ -39,7 +39,9 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "tvdc_rfft2",       "tvdc_solve",       "tvdc_irfft2",
                                     "tvdc_ystep",       "tvdc_adjoint",     "tvdc_dual",
                                     "spl_rfft2",        "spl_solve",        "spl_irfft2",
-                                    "spl_ystep"};
+                                    "spl_ystep",
+                                    "bpdn_dts",         "bpdn_iter",        "bpdn_joint_rows",
+                                    "bpdn_joint_apply", "bpdn_lsc"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -656,6 +658,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_tvd.inc"
 #include "api_tvdc.inc"
 #include "api_spline.inc"
+#include "api_bpdn.inc"
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {
     if (dims.dtype == SPORCO_AMD_F32) return new Csc<float>(dims, device, stream, dict_channels, depth);

@@ -1,0 +1,433 @@
+// csc_bpdn.hip -- the kernels of csc_bpdn.h: bpdn_dts, bpdn_iter, bpdn_joint_rows, bpdn_joint_apply, bpdn_lsc.
+// float32 / float64, 1 <= M, N <= kBpdnMaxDim, any K >= 1.  Compiled with -ffp-contract=off (Makefile): the two
+// product forms must round alike, every fused multiply-add here is spelled out.
+#include "csc_bpdn.h"
+#include "csc_kernels_dev.h"
+
+#include <algorithm>
+
+namespace sporco_amd {
+
+namespace {
+
+template <typename T> __device__ __forceinline__ T bp_abs(T v) { return v < T(0) ? -v : v; }
+// prox_l1: sign(v) max(0, |v| - alpha) (sporco/prox/_lp.py:144-183)
+template <typename T> __device__ __forceinline__ T bp_soft(T v, T alpha) {
+    const T b = bp_abs(v) - alpha;
+    return b > T(0) ? (v < T(0) ? -b : b) : T(0);
+}
+
+// OUT (lda rows, 16 NCT columns) = A . TILE, k over [0, Kd4).  ak: [Kd4][lda] k-major, zero padded, lda a multiple of
+// 16, Kd4 of 4; tile: [Kd4][ldb] in LDS, zero padded.  Wave w takes the slabs of rows 16 w, 16 (w + 4), ...; lane l
+// ends with rows i0 + 4 (l >> 4) + r, r < 4, of column 16 ct + (l & 15), handed to epi(row, column, value).
+template <typename T, int NCT, int FORM, typename Epi>
+__device__ __forceinline__ void bpdn_product(const T *__restrict__ ak, int lda, int Kd4, const T *tile, int ldb, Epi &&epi) {
+    const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x / kWave;
+    const int lc = lane & 15, lh = lane >> 4;
+    for (int i0 = wave * 16; i0 < lda; i0 += 16 * (kThreads / kWave)) {
+        T acc[NCT][4];
+#ifndef SPORCO_AMD_HOSTSIM
+        if constexpr (FORM == BPDN_FORM_MFMA) {
+            // A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15]; D: column l & 15, rows 4 (l >> 4) + r
+            sa_floatx4 c[NCT];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) c[ct] = sa_floatx4{0.f, 0.f, 0.f, 0.f};
+            const T *ap = ak + (int64_t)lh * lda + i0 + lc;
+            const T *bp = tile + lh * ldb + lc;
+            for (int k0 = 0; k0 < Kd4; k0 += 4) {
+                const float av = ap[(int64_t)k0 * lda];
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) c[ct] = sa_mfma_f32_16x16x4(av, bp[k0 * ldb + 16 * ct], c[ct]);
+            }
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                acc[ct][0] = c[ct].x;
+                acc[ct][1] = c[ct].y;
+                acc[ct][2] = c[ct].z;
+                acc[ct][3] = c[ct].w;
+            }
+        } else
+#endif
+        {
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[ct][r] = T(0);
+            const T *ap = ak + i0 + 4 * lh;
+            const T *bp = tile + lc;
+            for (int k = 0; k < Kd4; ++k) {
+                const Vec<T, 4> av = *reinterpret_cast<const Vec<T, 4> *>(ap + (int64_t)k * lda);
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+                    const T bv = bp[k * ldb + 16 * ct];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[ct][r] = fma1(av.v[r], bv, acc[ct][r]);
+                }
+            }
+        }
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) epi(i0 + 4 * lh + r, 16 * ct + lc, acc[ct][r]);
+    }
+}
+
+template <typename T, int KB> struct BpGeom {
+    static constexpr int LDB = KB == 32 ? 48 : 16;
+    static constexpr int NCT = KB / 16;
+    int M, N, M4, N4, M16, N16, R;
+    T *tb, *tx;
+    double *scratch;
+    __device__ __forceinline__ BpGeom(int M_, int N_) : M(M_), N(N_) {
+        M4 = (M + 3) & ~3;
+        N4 = (N + 3) & ~3;
+        M16 = (M + 15) & ~15;
+        N16 = (N + 15) & ~15;
+        R = M4 > N4 ? M4 : N4;
+        tb = dyn_lds<T>();
+        tx = tb + R * LDB;
+        scratch = reinterpret_cast<double *>(tx + R * LDB);
+    }
+    // rows [r0, r1) of a tile <- 0 (the padding of the k range; no later store touches it)
+    __device__ __forceinline__ void zero_rows(T *t, int r0, int r1) const {
+        for (int idx = (int)threadIdx.x; idx < (r1 - r0) * LDB; idx += kThreads) t[r0 * LDB + idx] = T(0);
+    }
+};
+
+// what the y and u steps leave of one element
+template <typename T>
+__device__ __forceinline__ void bp_ustep_sums(const BpdnArgs<T> &a, T x, T y, T uv, T ax, T yn, T w, T &un,
+                                              double (&acc)[kBpdnSums]) {
+    un = uv + (ax - yn);
+    const double r = (double)(x - yn), dy = (double)(yn - y);
+    acc[BPDN_R2] += r * r;
+    acc[BPDN_X2] += (double)x * (double)x;
+    acc[BPDN_Y2] += (double)yn * (double)yn;
+    acc[BPDN_S2] += dy * dy;
+    acc[BPDN_U2] += (double)un * (double)un;
+    acc[BPDN_L1] += (double)bp_abs(w * (a.geval_y ? yn : x));
+}
+
+// sum (D V - S)^2 over the block's columns, V the (M, KB) tile tv
+template <typename T, int KB, int FORM>
+__device__ __forceinline__ void bp_dfid(const BpdnArgs<T> &a, const BpGeom<T, KB> &g, const T *tv, int64_t c0, double &dfid) {
+    bpdn_product<T, BpGeom<T, KB>::NCT, FORM>(a.dtk, g.N16, g.M4, tv, BpGeom<T, KB>::LDB, [&](int i, int j, T v) {
+        const int64_t col = c0 + j;
+        if (i < g.N && col < a.K) {
+            const double d = (double)(v - a.s[(int64_t)i * a.K + col]);
+            dfid += d * d;
+        }
+    });
+}
+
+// this thread's rows t, t + 256 of the tile: sums of squares over the block's columns, in column order
+template <typename T, int KB>
+__device__ __forceinline__ void bp_row_sums(const BpGeom<T, KB> &g, const T *t, double (&racc)[2]) {
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        const int row = (int)threadIdx.x + rr * kThreads;
+        if (row < g.M) {
+            double s = 0.0;
+            for (int j = 0; j < KB; ++j) {
+                const double v = (double)t[row * BpGeom<T, KB>::LDB + j];
+                s += v * v;
+            }
+            racc[rr] += s;
+        }
+    }
+}
+template <typename T, int KB>
+__device__ __forceinline__ void bp_row_store(const BpGeom<T, KB> &g, const double (&racc)[2], double *rowp) {
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        const int row = (int)threadIdx.x + rr * kThreads;
+        if (row < g.M) rowp[(int64_t)blockIdx.x * g.M + row] = racc[rr];
+    }
+}
+
+template <typename T, int KB, int FORM> __global__ void __launch_bounds__(kThreads) bpdn_iter_kernel(const BpdnArgs<T> a) {
+    using G = BpGeom<T, KB>;
+    const G g(a.M, a.N);
+    const int64_t nblk = (a.K + KB - 1) / KB;
+    const bool relax = a.rlx != T(1);
+    const T rl1 = T(1) - a.rlx;
+    g.zero_rows(g.tb, g.M, g.M4);
+    g.zero_rows(g.tx, g.M, g.M4);
+    double acc[kBpdnSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double racc[2] = {0.0, 0.0}, raccx[2] = {0.0, 0.0};
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t c0 = blk * KB;
+        // B = D^T S + rho (Y - U), zero beyond the last column
+        for (int idx = (int)threadIdx.x; idx < g.M * KB; idx += kThreads) {
+            const int i = idx / KB, j = idx % KB;
+            const int64_t col = c0 + j, off = (int64_t)i * a.K + col;
+            T b = T(0);
+            if (col < a.K) {
+                b = a.dts[off] + a.rho * (a.y[off] - a.u_scale * a.u[off]);
+                if (a.bsave) a.bsave[off] = b;
+            }
+            g.tb[i * G::LDB + j] = b;
+        }
+        __syncthreads();
+        bpdn_product<T, G::NCT, FORM>(a.pk, g.M16, g.M4, g.tb, G::LDB, [&](int i, int j, T v) {
+            if (i < g.M) g.tx[i * G::LDB + j] = v;
+        });
+        __syncthreads();
+        for (int idx = (int)threadIdx.x; idx < g.M * KB; idx += kThreads) {
+            const int i = idx / KB, j = idx % KB;
+            const int64_t col = c0 + j, off = (int64_t)i * a.K + col;
+            T keep = T(0);
+            if (col < a.K) {
+                const T x = g.tx[i * G::LDB + j], y = a.y[off], uv = a.u_scale * a.u[off];
+                const T w = a.wl1 ? a.wl1[off] : a.wl1_s;
+                const T ax = relax ? a.rlx * x + rl1 * y : x;
+                const T z = bp_soft(ax + uv, a.lr * w);
+                if (a.joint) {
+                    a.z[off] = z;
+                    a.x[off] = x;
+                    keep = z;
+                } else {
+                    const T yn = (a.nonneg && z < T(0)) ? T(0) : z;
+                    T un;
+                    bp_ustep_sums(a, x, y, uv, ax, yn, w, un, acc);
+                    a.y[off] = yn;
+                    a.u[off] = un;
+                    if (a.want_x) a.x[off] = x;
+                    keep = a.feval_x ? x : yn;
+                }
+            }
+            g.tb[i * G::LDB + j] = keep;
+        }
+        __syncthreads();
+        if (a.joint) {
+            bp_row_sums<T, KB>(g, g.tb, racc);
+            if (a.rowpx) bp_row_sums<T, KB>(g, g.tx, raccx);
+        } else {
+            bp_dfid<T, KB, FORM>(a, g, g.tb, c0, acc[BPDN_DFID]);
+        }
+        __syncthreads();
+    }
+    if (a.joint) {
+        bp_row_store<T, KB>(g, racc, a.rowp);
+        if (a.rowpx) bp_row_store<T, KB>(g, raccx, a.rowpx);
+    } else {
+        block_sum_store<kBpdnSums>(acc, g.scratch, a.partials + (int64_t)blockIdx.x * kBpdnSums);
+    }
+}
+
+template <typename T, int KB, int FORM>
+__global__ void __launch_bounds__(kThreads) bpdn_joint_apply_kernel(const BpdnArgs<T> a) {
+    using G = BpGeom<T, KB>;
+    const G g(a.M, a.N);
+    const int64_t nblk = (a.K + KB - 1) / KB;
+    const bool relax = a.rlx != T(1);
+    const T rl1 = T(1) - a.rlx;
+    g.zero_rows(g.tb, g.M, g.M4);
+    g.zero_rows(g.tx, g.M, g.M4);
+    double acc[kBpdnSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double racc[2] = {0.0, 0.0};
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t c0 = blk * KB;
+        for (int idx = (int)threadIdx.x; idx < g.M * KB; idx += kThreads) {
+            const int i = idx / KB, j = idx % KB;
+            const int64_t col = c0 + j, off = (int64_t)i * a.K + col;
+            T keep = T(0), ykeep = T(0);
+            if (col < a.K) {
+                const T x = a.x[off], y = a.y[off], uv = a.u_scale * a.u[off];
+                const T w = a.wl1 ? a.wl1[off] : a.wl1_s;
+                const T ax = relax ? a.rlx * x + rl1 * y : x;
+                const T zs = a.rowf[i] * a.z[off];
+                const T yn = (a.nonneg && zs < T(0)) ? T(0) : zs;
+                T un;
+                bp_ustep_sums(a, x, y, uv, ax, yn, w, un, acc);
+                a.y[off] = yn;
+                a.u[off] = un;
+                keep = a.feval_x ? x : yn;
+                ykeep = yn;
+            }
+            g.tb[i * G::LDB + j] = keep;
+            g.tx[i * G::LDB + j] = ykeep;
+        }
+        __syncthreads();
+        bp_row_sums<T, KB>(g, g.tx, racc);
+        bp_dfid<T, KB, FORM>(a, g, g.tb, c0, acc[BPDN_DFID]);
+        __syncthreads();
+    }
+    bp_row_store<T, KB>(g, racc, a.rowp);
+    block_sum_store<kBpdnSums>(acc, g.scratch, a.partials + (int64_t)blockIdx.x * kBpdnSums);
+}
+
+template <typename T, int KB, int FORM> __global__ void __launch_bounds__(kThreads) bpdn_dts_kernel(const BpdnArgs<T> a) {
+    using G = BpGeom<T, KB>;
+    const G g(a.M, a.N);
+    const int64_t nblk = (a.K + KB - 1) / KB;
+    g.zero_rows(g.tb, g.N, g.N4);
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t c0 = blk * KB;
+        for (int idx = (int)threadIdx.x; idx < g.N * KB; idx += kThreads) {
+            const int i = idx / KB, j = idx % KB;
+            const int64_t col = c0 + j;
+            g.tb[i * G::LDB + j] = col < a.K ? a.s[(int64_t)i * a.K + col] : T(0);
+        }
+        __syncthreads();
+        bpdn_product<T, G::NCT, FORM>(a.dk, g.M16, g.N4, g.tb, G::LDB, [&](int i, int j, T v) {
+            const int64_t col = c0 + j;
+            if (i < g.M && col < a.K) a.dts[(int64_t)i * a.K + col] = v;
+        });
+        __syncthreads();
+    }
+}
+
+template <typename T, int KB, int FORM> __global__ void __launch_bounds__(kThreads) bpdn_lsc_kernel(const BpdnArgs<T> a) {
+    using G = BpGeom<T, KB>;
+    const G g(a.M, a.N);
+    const int64_t nblk = (a.K + KB - 1) / KB;
+    g.zero_rows(g.tb, g.M, g.M4);
+    g.zero_rows(g.tx, g.N, g.N4);
+    double acc[kBpdnLscSums] = {0.0, 0.0, 0.0};
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t c0 = blk * KB;
+        for (int idx = (int)threadIdx.x; idx < g.M * KB; idx += kThreads) {
+            const int i = idx / KB, j = idx % KB;
+            const int64_t col = c0 + j;
+            g.tb[i * G::LDB + j] = col < a.K ? a.x[(int64_t)i * a.K + col] : T(0);
+        }
+        __syncthreads();
+        bpdn_product<T, G::NCT, FORM>(a.dtk, g.N16, g.M4, g.tb, G::LDB, [&](int i, int j, T v) {
+            if (i < g.N) g.tx[i * G::LDB + j] = v;
+        });
+        __syncthreads();
+        bpdn_product<T, G::NCT, FORM>(a.dk, g.M16, g.N4, g.tx, G::LDB, [&](int i, int j, T v) {
+            const int64_t col = c0 + j;
+            if (i < g.M && col < a.K) {
+                const T ax = v + a.c * g.tb[i * G::LDB + j];
+                const T b = a.bsave[(int64_t)i * a.K + col];
+                const double d = (double)(ax - b);
+                acc[0] += d * d;
+                acc[1] += (double)ax * (double)ax;
+                acc[2] += (double)b * (double)b;
+            }
+        });
+        __syncthreads();
+    }
+    block_sum_store<kBpdnLscSums>(acc, g.scratch, a.partials + (int64_t)blockIdx.x * kBpdnLscSums);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+    bpdn_joint_rows_kernel(const double *rowp, int nb, int M, int mode, T mr, T *rowf, double *out, int slot) {
+    double acc[1] = {0.0};
+    for (int m = (int)threadIdx.x; m < M; m += kThreads) {
+        double s = 0.0;
+        for (int b = 0; b < nb; ++b) s += rowp[(int64_t)b * M + m];
+        if (mode == 0) {
+            // prox_l2 (sporco/prox/_lp.py:284-290): max(0, a - alpha) / a, zero at a zero row
+            const T nrm = (T)sqrt(s);
+            const T d = nrm - mr;
+            rowf[m] = nrm == T(0) ? T(0) : (d > T(0) ? d : T(0)) / nrm;
+        } else {
+            acc[0] += sqrt(s);
+        }
+    }
+    if (mode != 0) block_sum_store<1>(acc, dyn_lds<double>(), out + slot);
+}
+
+template <auto KERNEL, typename A> void bp_launch(int nb, size_t lds, hipStream_t st, const A &a) {
+    static PerDeviceOnce attr_set;
+    if (attr_set.first())
+        SA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   160 * 1024));
+    hipLaunchKernelGGL(KERNEL, dim3(nb), dim3(kThreads), lds, st, a);
+    SA_HIP(hipGetLastError());
+}
+
+template <typename T> void bp_check(const BpdnArgs<T> &a, const char *what) {
+    SA_REQUIRE(a.M >= 1 && a.M <= kBpdnMaxDim && a.N >= 1 && a.N <= kBpdnMaxDim && a.K >= 1 &&
+                   a.K < (int64_t)1 << 31 && a.KB == bpdn_kb<T>(a.M, a.N),
+               what);
+    SA_REQUIRE(bpdn_lds_bytes<T>(a.M, a.N) <= (size_t)160 * 1024, what);
+    SA_REQUIRE(a.form == BPDN_FORM_PLAIN || a.form == BPDN_FORM_MFMA, what);
+}
+
+// whether the launch uses the matrix instruction: float32 on the device, unless the plain form is asked for
+template <typename T> constexpr bool bp_has_mfma() {
+#ifdef SPORCO_AMD_HOSTSIM
+    return false;
+#else
+    return sizeof(T) == 4;
+#endif
+}
+
+#define SA_BP_DISPATCH(KERNEL, a, nb)                                                                              \
+    do {                                                                                                           \
+        const size_t lds_ = bpdn_lds_bytes<T>((a).M, (a).N);                                                       \
+        const bool mf_ = (a).form == BPDN_FORM_MFMA;                                                               \
+        if (mf_) SA_REQUIRE(bp_has_mfma<T>(), "bpdn: the matrix form exists in float32 on the device only");        \
+        if ((a).KB == 32) {                                                                                        \
+            if constexpr (bp_has_mfma<T>()) {                                                                      \
+                if (mf_) bp_launch<&KERNEL<T, 32, BPDN_FORM_MFMA>>(nb, lds_, st, a);                                \
+            }                                                                                                      \
+            if (!mf_) bp_launch<&KERNEL<T, 32, BPDN_FORM_PLAIN>>(nb, lds_, st, a);                                  \
+        } else {                                                                                                   \
+            if constexpr (bp_has_mfma<T>()) {                                                                      \
+                if (mf_) bp_launch<&KERNEL<T, 16, BPDN_FORM_MFMA>>(nb, lds_, st, a);                                \
+            }                                                                                                      \
+            if (!mf_) bp_launch<&KERNEL<T, 16, BPDN_FORM_PLAIN>>(nb, lds_, st, a);                                  \
+        }                                                                                                          \
+    } while (0)
+
+}  // namespace
+
+template <typename T> void launch_bpdn_dts(hipStream_t st, const BpdnArgs<T> &a) {
+    bp_check(a, "bpdn_dts: bad argument");
+    SA_REQUIRE(a.dk && a.s && a.dts, "bpdn_dts: null argument");
+    const int nb = bpdn_blocks(a.K, a.KB);
+    SA_BP_DISPATCH(bpdn_dts_kernel, a, nb);
+}
+
+template <typename T> int launch_bpdn_iter(hipStream_t st, const BpdnArgs<T> &a) {
+    bp_check(a, "bpdn_iter: bad argument");
+    SA_REQUIRE(a.pk && a.dtk && a.s && a.dts && a.x && a.y && a.u && a.rho > T(0), "bpdn_iter: null argument");
+    SA_REQUIRE(a.joint ? (a.z && a.rowp) : (a.partials != nullptr), "bpdn_iter: null argument");
+    const int nb = bpdn_blocks(a.K, a.KB);
+    SA_BP_DISPATCH(bpdn_iter_kernel, a, nb);
+    return nb;
+}
+
+template <typename T> int launch_bpdn_joint_apply(hipStream_t st, const BpdnArgs<T> &a) {
+    bp_check(a, "bpdn_joint_apply: bad argument");
+    SA_REQUIRE(a.dtk && a.s && a.x && a.y && a.u && a.z && a.rowf && a.rowp && a.partials, "bpdn_joint_apply: null argument");
+    const int nb = bpdn_blocks(a.K, a.KB);
+    SA_BP_DISPATCH(bpdn_joint_apply_kernel, a, nb);
+    return nb;
+}
+
+template <typename T> int launch_bpdn_lsc(hipStream_t st, const BpdnArgs<T> &a) {
+    bp_check(a, "bpdn_lsc: bad argument");
+    SA_REQUIRE(a.dk && a.dtk && a.x && a.bsave && a.partials, "bpdn_lsc: null argument");
+    const int nb = bpdn_blocks(a.K, a.KB);
+    SA_BP_DISPATCH(bpdn_lsc_kernel, a, nb);
+    return nb;
+}
+
+template <typename T>
+void launch_bpdn_joint_rows(hipStream_t st, const double *rowp, int nb, int M, int mode, T mr, T *rowf, double *out,
+                            int slot) {
+    SA_REQUIRE(rowp && nb >= 1 && nb <= kBpdnMaxBlocks && M >= 1 && M <= kBpdnMaxDim, "bpdn_joint_rows: bad argument");
+    SA_REQUIRE(mode == 0 ? rowf != nullptr : (out != nullptr && slot >= 0 && slot < kOutSlots),
+               "bpdn_joint_rows: null argument");
+    hipLaunchKernelGGL((bpdn_joint_rows_kernel<T>), dim3(1), dim3(kThreads), sizeof(double) * (kThreads / kWave), st, rowp,
+                       nb, M, mode, mr, rowf, out, slot);
+    SA_HIP(hipGetLastError());
+}
+
+#define SA_BPDN_INST(T)                                                                                     \
+    template void launch_bpdn_dts<T>(hipStream_t, const BpdnArgs<T> &);                                    \
+    template int launch_bpdn_iter<T>(hipStream_t, const BpdnArgs<T> &);                                    \
+    template int launch_bpdn_joint_apply<T>(hipStream_t, const BpdnArgs<T> &);                             \
+    template int launch_bpdn_lsc<T>(hipStream_t, const BpdnArgs<T> &);                                     \
+    template void launch_bpdn_joint_rows<T>(hipStream_t, const double *, int, int, int, T, T *, double *, int);
+SA_BPDN_INST(float)
+SA_BPDN_INST(double)
+
+}  // namespace sporco_amd

@@ -29,6 +29,7 @@
 #include "csc_tvd.h"
 #include "csc_tvdc.h"
 #include "csc_spline.h"
+#include "csc_bpdn.h"
 #include "fft.h"
 
 #include <atomic>
@@ -128,6 +129,11 @@ enum ProfSlot {
     PS_SPL_SOLVE,               // ... post-twiddle, Gamma, pre-twiddle in place, Reg and the LinSolveCheck sums
     PS_SPL_IRFFT2,              // ... the inverse transform pair: X in permuted order
     PS_SPL_YSTEP,               // ... relax + y step + u step + sums + the permuted arrays of the next x step
+    PS_BPDN_DTS,                // BPDN / BPDNJoint / ElasticNet: D^T S (csc_bpdn.h)
+    PS_BPDN_ITER,               // ... the whole iteration of a column block (joint: up to the l1 shrinkage)
+    PS_BPDN_JOINT_ROWS,         // ... joint: the fixed-order row reductions
+    PS_BPDN_JOINT_APPLY,        // ... joint: row scaling, u step, sums
+    PS_BPDN_LSC,                // ... the relative residual of the x step (LinSolveCheck)
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -373,6 +379,21 @@ SplBase *make_spl(int dtype, int H, int W, int64_t P, int device, void *stream);
 // the stateless orthonormal DCT-II (inverse: its inverse) over axes (0, 1) of an (H, W, P) array
 void spl_dct_dispatch(int dtype, int H, int W, int64_t P, const void *in, void *out, bool inverse, bool on_device);
 
+// The handle of BPDN, BPDNJoint and ElasticNet (api_bpdn.inc): the arrays of one (N, M, K) problem, the dictionary and
+// the solve matrix in the order the product routine reads them, and a stream.
+struct BpdnBase {
+    virtual ~BpdnBase() {}
+    virtual void sync() = 0;
+    virtual void plan(int64_t out[4]) = 0;
+    virtual void set_dict(const void *D) = 0;
+    virtual void set_solve(const void *P) = 0;
+    virtual void upload(int var, const void *src) = 0;
+    virtual void download(int var, void *dst) = 0;
+    virtual void iter(const sporco_amd_bpdn_params &p, double *out_host) = 0;
+    Profiler prof;
+};
+BpdnBase *make_bpdn(int dtype, int N, int M, int64_t K, int device, void *stream);
+
 // the one place that instantiates Csc<float> / Csc<double> (csc_api.hip)
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream,
                   int depth = 1);
@@ -402,6 +423,11 @@ struct sporco_amd_tvdc {
 
 struct sporco_amd_spl {
     std::unique_ptr<sporco_amd::SplBase> impl;
+    int device;
+};
+
+struct sporco_amd_bpdn {
+    std::unique_ptr<sporco_amd::BpdnBase> impl;
     int device;
 };
 

@@ -101,6 +101,14 @@ __device__ __forceinline__ void sa_stream_store4(float *p, const float (&v)[4]) 
         *reinterpret_cast<sa_floatx4 *>(p) = t;
 }
 
+// D (16 x 16) = A (16 x 4) . B (4 x 16) + C on the matrix cores with float32 operands (v_mfma_f32_16x16x4_f32): lane l
+// gives a = A[l & 15][l >> 4] and b = B[l >> 4][l & 15] and holds rows 4 (l >> 4) + r, r = 0..3, of column l & 15 of
+// C and D.  Exact float32: D = fma(a3, b3, fma(a2, b2, fma(a1, b1, fma(a0, b0, C)))), one rounding per product.
+// (The CPU simulator has no counterpart: kernels that use it compile their plain form there.)
+__device__ __forceinline__ sa_floatx4 sa_mfma_f32_16x16x4(float a, float b, sa_floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
 // Wave-uniform loads of read-only data through the scalar cache (s_load_dword[x2]):
 // the pointer is re-typed to the constant address space, which is what lets the
 // compiler keep them scalar after barriers/fences (a plain global load of a uniform

@@ -36,10 +36,11 @@ ALIASES = {
     'sporco.pgm.momentum': 'sporco_amd.pgm.momentum',
     'sporco.admm.tvl1': 'sporco_amd.admm.tvl1',
     'sporco.admm.tvl2': 'sporco_amd.admm.tvl2',
+    'sporco.admm.bpdn': 'sporco_amd.admm.bpdn',
 }
 FILES = ['admm/test_cbpdn.py', 'admm/test_ccmod.py', 'admm/test_ccmodmd.py', 'pgm/test_cbpdn.py',
          'pgm/test_ccmod.py', 'dictlrn/test_cbpdndl.py', 'dictlrn/test_cbpdndlmd.py',
-         'dictlrn/test_onlinecdl.py', 'admm/test_tvl1.py', 'admm/test_tvl2.py']
+         'dictlrn/test_onlinecdl.py', 'admm/test_tvl1.py', 'admm/test_tvl2.py', 'admm/test_bpdn.py']
 
 
 def main():
