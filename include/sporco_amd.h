@@ -44,6 +44,7 @@
  *   SPORCO_AMD_PDL1_GENERIC=1   (tests) pdl1_solve in its one-thread-per-system form on every shape
  *   SPORCO_AMD_BPDN_PLAIN=1     (tests, measurements) the float32 products of the bpdn handle as fused
  *                               multiply-add chains instead of the matrix instruction; same bits
+ *   SPORCO_AMD_CMOD_PLAIN=1     (tests, measurements) the same for the float32 products of the cmod handle
  *   SPORCO_AMD_CG_HOST=1        CG dictionary update: the scalars read back every iteration
  *   SPORCO_AMD_PLACEMENT=0|force   no placement search for concurrently written arrays / the search
  *                               (and the striped column output) also for small arrays -- tests
@@ -1296,6 +1297,59 @@ int sporco_amd_bpdn_iter(sporco_amd_bpdn_t h, const sporco_amd_bpdn_params *p, d
 /* Per-kernel event timing of the handle's launches, as sporco_amd_csc_profile / _profile_read. */
 int sporco_amd_bpdn_profile(sporco_amd_bpdn_t h, int enable);
 int sporco_amd_bpdn_profile_read(sporco_amd_bpdn_t h, int slot, const char **name, double *total_ms,
+                                 int64_t *count);
+/* *out = the device buffer of variable `var`, valid while the handle lives (NULL: the weight is a scalar).  What
+ * lets another handle read the coefficients in place (sporco_amd_cmod_set_coef with on_device). */
+int sporco_amd_bpdn_devptr(sporco_amd_bpdn_t h, int var, void **out);
+
+/* ---- dense dictionary update: sporco.admm.cmod CnstrMOD (sporco/admm/cmod.py:21-342) ----
+ *     minimise ||D Z - S||^2  such that  ||d_m|| = 1 [, mean(d_m) = 0]   on  d = g,
+ * Z (M, K), S (N, K), X / Y / U (N, M), every array row-major as NumPy has it.  set_coef forms Z Z^T and S Z^T on
+ * the device, reduced over K (csrc/csc_cmod.h), and leaves them in double for the caller, who forms
+ * Q = (Z Z^T + rho I)^-1 and sets it again whenever rho changes.  The x step is X = (S Z^T + rho (Y - U)) Q, the y
+ * step the projection onto unit-norm (zero-mean) columns.  The products run on the float32 matrix instruction
+ * (float64, or SPORCO_AMD_CMOD_PLAIN: as fma chains with the same bits).  Y and U start at zero. */
+typedef struct sporco_amd_cmod *sporco_amd_cmod_t;
+#define SPORCO_AMD_CMOD_MAX_DIM 512 /* the largest N and M */
+#define SPORCO_AMD_CMOD_X 0      /* (N,M)  the result of the x step                                          */
+#define SPORCO_AMD_CMOD_Y 1      /* (N,M)                                                                    */
+#define SPORCO_AMD_CMOD_U 2      /* (N,M)  (without a pending u_scale)                                       */
+#define SPORCO_AMD_CMOD_SZT 3    /* (N,M)  S Z^T in the handle's precision (an upload only prefills: tests)  */
+#define SPORCO_AMD_CMOD_G 4      /* (M,M)  Z Z^T, doubles whatever the handle's dtype (likewise)             */
+#define SPORCO_AMD_CMOD_SZTD 5   /* (N,M)  S Z^T, doubles (likewise)                                         */
+typedef struct {
+    double rho, rlx;
+    double u_scale;           /* pending U /= rsf (admm.py:573): the iteration applies it                    */
+    int32_t zero_mean;        /* ZeroMean: the projection subtracts the column means first                   */
+    int32_t feval_x;          /* DFid at X, else at Y                                                        */
+    int32_t geval_y;          /* Cnstr at Y, else at X                                                       */
+    int32_t want_dfid;        /* form OUT_DFID (one more launch that reads Z and S)                          */
+} sporco_amd_cmod_params;
+int sporco_amd_cmod_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_cmod_t *out);
+int sporco_amd_cmod_destroy(sporco_amd_cmod_t h);
+int sporco_amd_cmod_sync(sporco_amd_cmod_t h);
+/* out[0] = columns of K staged per step, out[1] = columns of a slab, out[2] = slabs, out[3], out[4] = row and
+ * column blocks of the output, out[5] = 1 where the products use the matrix instruction, out[6], out[7] = bytes
+ * of LDS of a workgroup of cmod_gram and of cmod_iter. */
+int sporco_amd_cmod_plan(sporco_amd_cmod_t h, int64_t out[8]);
+/* S (N, K) / Z (M, K) in the handle's precision.  on_device: a device pointer that is read in place, not copied;
+ * it stays valid and unchanged until the next set_signal / set_coef or the handle's end (Z is read again by every
+ * iteration that forms OUT_DFID).  set_coef needs S; it runs cmod_gram and cmod_gram_reduce. */
+int sporco_amd_cmod_set_signal(sporco_amd_cmod_t h, const void *S, int on_device);
+int sporco_amd_cmod_set_coef(sporco_amd_cmod_t h, const void *Z, int on_device);
+/* Q: host (M, M) in the handle's precision. */
+int sporco_amd_cmod_set_solve(sporco_amd_cmod_t h, const void *Q);
+/* Copy a host array in or out. */
+int sporco_amd_cmod_upload(sporco_amd_cmod_t h, int var, const void *src);
+int sporco_amd_cmod_download(sporco_amd_cmod_t h, int var, void *dst);
+/* One iteration: cmod_rhs, cmod_iter [, cmod_dfid], one reduction, one host read.  out: OUT_R2 = ||X - Y||^2,
+ * OUT_AX2 = ||X||^2, OUT_Y2, OUT_S2 = ||Y - Yprev||^2 (rho applied by the host), OUT_U2, OUT_CNSTR =
+ * ||Pcn(g) - g||^2, OUT_DFID = ||f Z - S||^2 (the host halves it).  U is stored with u_scale applied. */
+int sporco_amd_cmod_iter(sporco_amd_cmod_t h, const sporco_amd_cmod_params *p, double out[SPORCO_AMD_OUT_COUNT]);
+/* out[OUT_DFID] = ||V Z - S||^2 for V = variable `var` (X or Y) and the Z and S in use. */
+int sporco_amd_cmod_dfid(sporco_amd_cmod_t h, int var, double out[SPORCO_AMD_OUT_COUNT]);
+int sporco_amd_cmod_profile(sporco_amd_cmod_t h, int enable);
+int sporco_amd_cmod_profile_read(sporco_amd_cmod_t h, int slot, const char **name, double *total_ms,
                                  int64_t *count);
 
 #ifdef __cplusplus

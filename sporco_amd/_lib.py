@@ -117,7 +117,11 @@ EXPORTS = (
     'sporco_amd_spl_profile', 'sporco_amd_spl_profile_read', 'sporco_amd_dctii', 'sporco_amd_idctii',
     'sporco_amd_bpdn_create', 'sporco_amd_bpdn_destroy', 'sporco_amd_bpdn_sync', 'sporco_amd_bpdn_plan',
     'sporco_amd_bpdn_set_dict', 'sporco_amd_bpdn_set_solve', 'sporco_amd_bpdn_upload', 'sporco_amd_bpdn_download',
-    'sporco_amd_bpdn_iter', 'sporco_amd_bpdn_profile', 'sporco_amd_bpdn_profile_read',
+    'sporco_amd_bpdn_iter', 'sporco_amd_bpdn_profile', 'sporco_amd_bpdn_profile_read', 'sporco_amd_bpdn_devptr',
+    'sporco_amd_cmod_create', 'sporco_amd_cmod_destroy', 'sporco_amd_cmod_sync', 'sporco_amd_cmod_plan',
+    'sporco_amd_cmod_set_signal', 'sporco_amd_cmod_set_coef', 'sporco_amd_cmod_set_solve', 'sporco_amd_cmod_upload',
+    'sporco_amd_cmod_download', 'sporco_amd_cmod_iter', 'sporco_amd_cmod_dfid', 'sporco_amd_cmod_profile',
+    'sporco_amd_cmod_profile_read',
 )
 
 
@@ -220,6 +224,17 @@ class BpdnParams(ctypes.Structure):
 
 BPDN_S, BPDN_X, BPDN_Y, BPDN_U, BPDN_WL1, BPDN_DTS = range(6)
 BPDN_MAX_DIM = 512
+
+
+class CmodParams(ctypes.Structure):
+    """sporco_amd_cmod_params: scalars of one CnstrMOD iteration."""
+    _fields_ = [('rho', ctypes.c_double), ('rlx', ctypes.c_double), ('u_scale', ctypes.c_double),
+                ('zero_mean', ctypes.c_int32), ('feval_x', ctypes.c_int32), ('geval_y', ctypes.c_int32),
+                ('want_dfid', ctypes.c_int32)]
+
+
+CMOD_X, CMOD_Y, CMOD_U, CMOD_SZT, CMOD_G, CMOD_SZTD = range(6)
+CMOD_MAX_DIM = 512             # SPORCO_AMD_CMOD_MAX_DIM
 
 REDUCE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
 EUNSUPPORTED = -5
@@ -468,6 +483,19 @@ def load(path=None):
         'sporco_amd_bpdn_iter': [vp, ctypes.POINTER(BpdnParams), dptr],
         'sporco_amd_bpdn_profile': [vp, ctypes.c_int],
         'sporco_amd_bpdn_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
+                                         ctypes.POINTER(i64)],
+        'sporco_amd_bpdn_devptr': [vp, ctypes.c_int, ctypes.POINTER(vp)],
+        'sporco_amd_cmod_create': [ctypes.c_int, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_cmod_destroy': [vp], 'sporco_amd_cmod_sync': [vp],
+        'sporco_amd_cmod_plan': [vp, ctypes.POINTER(i64)],
+        'sporco_amd_cmod_set_signal': [vp, vp, ctypes.c_int], 'sporco_amd_cmod_set_coef': [vp, vp, ctypes.c_int],
+        'sporco_amd_cmod_set_solve': [vp, vp],
+        'sporco_amd_cmod_upload': [vp, ctypes.c_int, vp],
+        'sporco_amd_cmod_download': [vp, ctypes.c_int, vp],
+        'sporco_amd_cmod_iter': [vp, ctypes.POINTER(CmodParams), dptr],
+        'sporco_amd_cmod_dfid': [vp, ctypes.c_int, dptr],
+        'sporco_amd_cmod_profile': [vp, ctypes.c_int],
+        'sporco_amd_cmod_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                          ctypes.POINTER(i64)],
         'sporco_amd_spl_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                         ctypes.POINTER(i64)],
@@ -1565,6 +1593,16 @@ class BpdnHandle(object):
         check(self._lib.sporco_amd_bpdn_iter(self._h, ctypes.byref(params), out))
         return list(out)
 
+    def device_view(self, var):
+        """A :class:`sporco_amd.device.DeviceArray` over the buffer of variable ``var``: no copy, and the view
+        keeps this handle alive.  It shows whatever the handle's calls leave in the buffer."""
+        from .device import DeviceArray
+        p = ctypes.c_void_p()
+        check(self._lib.sporco_amd_bpdn_devptr(self._h, int(var), ctypes.byref(p)))
+        if not p.value:
+            raise ValueError("the variable has no device array")
+        return DeviceArray(self._shape(var), self.dtype, ptr=p.value, base=self)
+
     def profile(self, enable):
         check(self._lib.sporco_amd_bpdn_profile(self._h, 1 if enable else 0))
 
@@ -1574,6 +1612,117 @@ class BpdnHandle(object):
         for slot in range(self._lib.sporco_amd_profile_slots()):
             name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
             check(self._lib.sporco_amd_bpdn_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
+                                                         ctypes.byref(cnt)))
+            if cnt.value:
+                res[name.value.decode()] = (ms.value, cnt.value)
+        return res
+
+
+class CmodHandle(object):
+    """Owner of one device-side CnstrMOD problem (sporco_amd_cmod_*): Z (M, K) and S (N, K), host arrays that are
+    copied or :class:`sporco_amd.device.DeviceArray` that are read in place (the handle keeps them alive);
+    X / Y / U (N, M), host arrays in and out."""
+
+    def __init__(self, N, M, K, dtype, device=0, stream=None):
+        self.dims = (int(N), int(M), int(K))
+        self.dtype = np.dtype(dtype)
+        h = ctypes.c_void_p()
+        check(lib().sporco_amd_cmod_create(dtype_code(dtype), int(N), int(M), int(K), int(device),
+                                           ctypes.c_void_p(stream or 0), ctypes.byref(h)))
+        self._h = h
+        self._lib = lib()
+        self._keep = {}
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sporco_amd_cmod_destroy(self._h)
+            self._h = None
+            self._keep = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        check(self._lib.sporco_amd_cmod_sync(self._h))
+
+    def plan(self):
+        """``dict(KS, slab, slabs, row_blocks, col_blocks, mfma, lds_gram, lds_iter)``: the columns of K staged per
+        step, the columns of a slab, the slabs, the 64 x 64 blocks of the output of cmod_gram, whether the products
+        use the matrix instruction, the bytes of LDS of a workgroup of cmod_gram and cmod_iter."""
+        out = (ctypes.c_int64 * 8)()
+        check(self._lib.sporco_amd_cmod_plan(self._h, out))
+        return dict(zip(('KS', 'slab', 'slabs', 'row_blocks', 'col_blocks', 'mfma', 'lds_gram', 'lds_iter'),
+                        (int(v) for v in out)))
+
+    def _shape(self, var):
+        N, M, K = self.dims
+        return (M, M) if var == CMOD_G else (N, M)
+
+    def _dtype(self, var):
+        return np.dtype(np.float64) if var in (CMOD_G, CMOD_SZTD) else self.dtype
+
+    def _set_big(self, fn, key, a, rows):
+        shape = (rows, self.dims[2])
+        if isinstance(a, np.ndarray):
+            a = _carr(a, self.dtype)
+            if a.shape != shape:
+                raise ValueError("array of shape %s where %s is expected" % (a.shape, shape))
+            check(fn(self._h, _ptr(a), 0))
+            self._keep.pop(key, None)
+            return
+        if tuple(a.shape) != shape or a.dtype != self.dtype:
+            raise ValueError("device array of shape %s and dtype %s where %s, %s is expected"
+                             % (tuple(a.shape), a.dtype, shape, self.dtype))
+        check(fn(self._h, ctypes.c_void_p(a.ptr), 1))
+        self._keep[key] = a
+
+    def set_signal(self, S):
+        self._set_big(self._lib.sporco_amd_cmod_set_signal, 'S', S, self.dims[0])
+
+    def set_coef(self, Z):
+        """Take Z and form Z Z^T and S Z^T on the device."""
+        self._set_big(self._lib.sporco_amd_cmod_set_coef, 'Z', Z, self.dims[1])
+
+    def set_solve(self, Q):
+        Q = _carr(Q, self.dtype)
+        if Q.shape != (self.dims[1], self.dims[1]):
+            raise ValueError("solve matrix of shape %s where %s is expected" % (Q.shape, (self.dims[1],) * 2))
+        check(self._lib.sporco_amd_cmod_set_solve(self._h, _ptr(Q)))
+
+    def upload(self, var, a):
+        a = _carr(a, self._dtype(var))
+        if a.shape != self._shape(var):
+            raise ValueError("array of shape %s where %s is expected" % (a.shape, self._shape(var)))
+        check(self._lib.sporco_amd_cmod_upload(self._h, int(var), _ptr(a)))
+
+    def download(self, var):
+        out = np.empty(self._shape(var), dtype=self._dtype(var))
+        check(self._lib.sporco_amd_cmod_download(self._h, int(var), _ptr(out)))
+        return out
+
+    def iter(self, params):
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_cmod_iter(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def dfid(self, var):
+        """``||V Z - S||^2`` for V = X or Y."""
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_cmod_dfid(self._h, int(var), out))
+        return out[OUT_DFID]
+
+    def profile(self, enable):
+        check(self._lib.sporco_amd_cmod_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self):
+        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
+        res = {}
+        for slot in range(self._lib.sporco_amd_profile_slots()):
+            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
+            check(self._lib.sporco_amd_cmod_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
                                                          ctypes.byref(cnt)))
             if cnt.value:
                 res[name.value.decode()] = (ms.value, cnt.value)

@@ -243,6 +243,11 @@ class GenericBPDN(admm.ADMMEqual):
         """The final coefficient array (bpdn.py:185-188)."""
         return self.Y
 
+    def getcoef_device(self):
+        """``Y`` as a :class:`sporco_amd.device.DeviceArray` over the handle's own buffer: no copy; the view keeps
+        the handle alive and shows what later iterations leave there."""
+        return self._dev.device_view(_lib.BPDN_Y)
+
     def getmin(self):
         return self.X if self.opt['ReturnX'] else self.Y
 

@@ -146,6 +146,7 @@ template <typename T> struct Bpdn : BpdnBase {
         default: throw Error(SPORCO_AMD_EINVAL, "bpdn: unknown array id");
         }
     }
+    void *var_ptr(int var) override { return var_buf(var); }
     size_t var_bytes(int var) const { return sizeof(T) * (size_t)(var == SPORCO_AMD_BPDN_S ? N : M) * K; }
     void upload(int var, const void *src) override {
         // (X and D^T S are results: setting them only prefills what the next iteration / set_dict overwrites)

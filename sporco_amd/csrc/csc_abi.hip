@@ -1338,4 +1338,141 @@ int sporco_amd_bpdn_profile_read(sporco_amd_bpdn_t h, int slot, const char **nam
     SA_API_END
 }
 
+int sporco_amd_bpdn_devptr(sporco_amd_bpdn_t h, int var, void **out) {
+    SA_API_BEGIN
+    SA_BPDN_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    *out = h->impl->var_ptr(var);
+    SA_API_END
+}
+
+// ---- CnstrMOD: a handle of its own (csc_impl.h CmodBase) ----------------------------------------------------
+#define SA_CMOD_HANDLE(h)                                                              \
+    SA_REQUIRE((h) != nullptr && (h)->impl, "null cmod handle");                       \
+    SA_HIP(hipSetDevice((h)->device));
+
+int sporco_amd_cmod_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_cmod_t *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out != nullptr, "null argument");
+    SA_REQUIRE(N >= 1 && M >= 1 && K >= 1, "cmod: N >= 1, M >= 1, K >= 1");
+    static_assert(SPORCO_AMD_CMOD_MAX_DIM == kCmodMaxDim, "one limit for the cmod handle");
+    SA_REQUIRE(N <= SPORCO_AMD_CMOD_MAX_DIM && M <= SPORCO_AMD_CMOD_MAX_DIM,
+               "cmod: the kernels serve dictionaries of up to 512 rows and 512 columns");
+    SA_REQUIRE(K < ((int64_t)1 << 31), "cmod: fewer than 2^31 signals");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    std::unique_ptr<sporco_amd_cmod> h(new sporco_amd_cmod);
+    h->device = device;
+    h->impl.reset(make_cmod(dtype, N, M, K, device, stream));
+    *out = h.release();
+    SA_API_END
+}
+
+int sporco_amd_cmod_destroy(sporco_amd_cmod_t h) {
+    SA_API_BEGIN
+    if (h) {
+        (void)hipSetDevice(h->device);
+        delete h;
+    }
+    SA_API_END
+}
+
+int sporco_amd_cmod_sync(sporco_amd_cmod_t h) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->sync();
+    SA_API_END
+}
+
+int sporco_amd_cmod_plan(sporco_amd_cmod_t h, int64_t out[8]) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    h->impl->plan(out);
+    SA_API_END
+}
+
+int sporco_amd_cmod_set_signal(sporco_amd_cmod_t h, const void *S, int on_device) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->set_signal(S, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_cmod_set_coef(sporco_amd_cmod_t h, const void *Z, int on_device) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->set_coef(Z, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_cmod_set_solve(sporco_amd_cmod_t h, const void *Q) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->set_solve(Q);
+    SA_API_END
+}
+
+int sporco_amd_cmod_upload(sporco_amd_cmod_t h, int var, const void *src) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->upload(var, src);
+    SA_API_END
+}
+
+int sporco_amd_cmod_download(sporco_amd_cmod_t h, int var, void *dst) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->download(var, dst);
+    SA_API_END
+}
+
+int sporco_amd_cmod_iter(sporco_amd_cmod_t h, const sporco_amd_cmod_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
+    h->impl->iter(*p, out);
+    SA_API_END
+}
+
+int sporco_amd_cmod_dfid(sporco_amd_cmod_t h, int var, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    h->impl->dfid(var, out);
+    SA_API_END
+}
+
+int sporco_amd_cmod_profile(sporco_amd_cmod_t h, int enable) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->sync();
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (enable)
+        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
+            hipEvent_t e;
+            SA_HIP(hipEventCreate(&e));
+            pr.pool.push_back(e);
+        }
+    pr.on = enable != 0;
+    SA_API_END
+}
+
+int sporco_amd_cmod_profile_read(sporco_amd_cmod_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (name) *name = kProfNames[slot];
+    if (total_ms) *total_ms = pr.total_ms[slot];
+    if (launches) *launches = pr.count[slot];
+    pr.total_ms[slot] = 0.0;
+    pr.count[slot] = 0;
+    SA_API_END
+}
+
 }  // extern "C"

@@ -41,7 +41,9 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "spl_rfft2",        "spl_solve",        "spl_irfft2",
                                     "spl_ystep",
                                     "bpdn_dts",         "bpdn_iter",        "bpdn_joint_rows",
-                                    "bpdn_joint_apply", "bpdn_lsc"};
+                                    "bpdn_joint_apply", "bpdn_lsc",
+                                    "cmod_gram",        "cmod_gram_reduce", "cmod_rhs",
+                                    "cmod_iter",        "cmod_dfid"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -659,6 +661,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_tvdc.inc"
 #include "api_spline.inc"
 #include "api_bpdn.inc"
+#include "api_cmod.inc"
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {
     if (dims.dtype == SPORCO_AMD_F32) return new Csc<float>(dims, device, stream, dict_channels, depth);

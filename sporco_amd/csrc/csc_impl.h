@@ -30,6 +30,7 @@
 #include "csc_tvdc.h"
 #include "csc_spline.h"
 #include "csc_bpdn.h"
+#include "csc_cmod.h"
 #include "fft.h"
 
 #include <atomic>
@@ -134,6 +135,11 @@ enum ProfSlot {
     PS_BPDN_JOINT_ROWS,         // ... joint: the fixed-order row reductions
     PS_BPDN_JOINT_APPLY,        // ... joint: row scaling, u step, sums
     PS_BPDN_LSC,                // ... the relative residual of the x step (LinSolveCheck)
+    PS_CMOD_GRAM,               // CnstrMOD: the slab partials of [Z; S] Z^T (csc_cmod.h)
+    PS_CMOD_GRAM_REDUCE,        // ... added in slab order
+    PS_CMOD_RHS,                // ... the right-hand side of the x step
+    PS_CMOD_ITER,               // ... the whole iteration of a block of 16 dictionary columns
+    PS_CMOD_DFID,               // ... sum (F Z - S)^2
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -390,9 +396,27 @@ struct BpdnBase {
     virtual void upload(int var, const void *src) = 0;
     virtual void download(int var, void *dst) = 0;
     virtual void iter(const sporco_amd_bpdn_params &p, double *out_host) = 0;
+    virtual void *var_ptr(int var) = 0;      // the device buffer of a variable (nullptr: not allocated)
     Profiler prof;
 };
 BpdnBase *make_bpdn(int dtype, int N, int M, int64_t K, int device, void *stream);
+
+// The handle of CnstrMOD (api_cmod.inc): the dictionary variables of one (N, M, K) problem in the order the product
+// routine reads them, the Gram matrices of the coefficients, its own or a borrowed Z and S, and a stream.
+struct CmodBase {
+    virtual ~CmodBase() {}
+    virtual void sync() = 0;
+    virtual void plan(int64_t out[8]) = 0;
+    virtual void set_signal(const void *S, bool on_device) = 0;
+    virtual void set_coef(const void *Z, bool on_device) = 0;
+    virtual void set_solve(const void *Q) = 0;
+    virtual void upload(int var, const void *src) = 0;
+    virtual void download(int var, void *dst) = 0;
+    virtual void iter(const sporco_amd_cmod_params &p, double *out_host) = 0;
+    virtual void dfid(int var, double *out_host) = 0;
+    Profiler prof;
+};
+CmodBase *make_cmod(int dtype, int N, int M, int64_t K, int device, void *stream);
 
 // the one place that instantiates Csc<float> / Csc<double> (csc_api.hip)
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream,
@@ -428,6 +452,11 @@ struct sporco_amd_spl {
 
 struct sporco_amd_bpdn {
     std::unique_ptr<sporco_amd::BpdnBase> impl;
+    int device;
+};
+
+struct sporco_amd_cmod {
+    std::unique_ptr<sporco_amd::CmodBase> impl;
     int device;
 };
 

@@ -37,10 +37,13 @@ ALIASES = {
     'sporco.admm.tvl1': 'sporco_amd.admm.tvl1',
     'sporco.admm.tvl2': 'sporco_amd.admm.tvl2',
     'sporco.admm.bpdn': 'sporco_amd.admm.bpdn',
+    'sporco.admm.cmod': 'sporco_amd.admm.cmod',
+    'sporco.dictlrn.bpdndl': 'sporco_amd.dictlrn.bpdndl',
 }
 FILES = ['admm/test_cbpdn.py', 'admm/test_ccmod.py', 'admm/test_ccmodmd.py', 'pgm/test_cbpdn.py',
          'pgm/test_ccmod.py', 'dictlrn/test_cbpdndl.py', 'dictlrn/test_cbpdndlmd.py',
-         'dictlrn/test_onlinecdl.py', 'admm/test_tvl1.py', 'admm/test_tvl2.py', 'admm/test_bpdn.py']
+         'dictlrn/test_onlinecdl.py', 'admm/test_tvl1.py', 'admm/test_tvl2.py', 'admm/test_bpdn.py',
+         'admm/test_cmod.py', 'dictlrn/test_bpdndl.py']
 
 
 def main():
