@@ -45,6 +45,8 @@
  *   SPORCO_AMD_BPDN_PLAIN=1     (tests, measurements) the float32 products of the bpdn handle as fused
  *                               multiply-add chains instead of the matrix instruction; same bits
  *   SPORCO_AMD_CMOD_PLAIN=1     (tests, measurements) the same for the float32 products of the cmod handle
+ *   SPORCO_AMD_RPCA_PLAIN=1     (tests, measurements) the float64 Gram products and the float32 product with T of
+ *                               the rpca handle as fused multiply-add chains (the latter with the same bits)
  *   SPORCO_AMD_CG_HOST=1        CG dictionary update: the scalars read back every iteration
  *   SPORCO_AMD_PLACEMENT=0|force   no placement search for concurrently written arrays / the search
  *                               (and the striped column output) also for small arrays -- tests
@@ -1350,6 +1352,56 @@ int sporco_amd_cmod_iter(sporco_amd_cmod_t h, const sporco_amd_cmod_params *p, d
 int sporco_amd_cmod_dfid(sporco_amd_cmod_t h, int var, double out[SPORCO_AMD_OUT_COUNT]);
 int sporco_amd_cmod_profile(sporco_amd_cmod_t h, int enable);
 int sporco_amd_cmod_profile_read(sporco_amd_cmod_t h, int slot, const char **name, double *total_ms,
+                                 int64_t *count);
+
+/* ---- robust PCA: sporco.admm.rpca RobustPCA (sporco/admm/rpca.py:23-262) and sporco.prox prox_nuclear ----
+ *     minimise ||X||_* + lambda ||Y||_1  such that  X + Y = S,
+ * S, X, Y, U (R, C) row-major as NumPy has them, n = min(R, C) <= SPORCO_AMD_RPCA_MAX_DIM, R C < 2^31.  The x step
+ * needs no SVD on the device: sporco_amd_rpca_gram leaves the n x n Gram matrix G of V = S - Y - U (V^T V for
+ * R >= C, else V V^T; csrc/csc_rpca.h) in double, the caller takes eigh(G) = W diag(sigma^2) W^T and hands
+ * T = W diag(max(0, 1 - (1 / rho) / sigma)) W^T to sporco_amd_rpca_iter, which forms X = V T (T V), relaxes, shrinks
+ * Y, updates U and sums in one launch.  Gram products run on the float64 matrix instruction for both dtypes, the
+ * product with T on the float32 one (float64: fma chains); SPORCO_AMD_RPCA_PLAIN=1 makes fma chains of both.
+ * X, Y, U start at zero. */
+typedef struct sporco_amd_rpca *sporco_amd_rpca_t;
+#define SPORCO_AMD_RPCA_MAX_DIM 512 /* the largest min(R, C) */
+#define SPORCO_AMD_RPCA_X 0      /* (R,C)  the result of the x step (of sporco_amd_rpca_apply)                */
+#define SPORCO_AMD_RPCA_Y 1      /* (R,C)                                                                    */
+#define SPORCO_AMD_RPCA_U 2      /* (R,C)  (without a pending u_scale)                                       */
+#define SPORCO_AMD_RPCA_V_SYU 0  /* sporco_amd_rpca_gram of S - Y - u_scale U: the x step                     */
+#define SPORCO_AMD_RPCA_V_SY 1   /* ... of S - Y: the nuclear norm term evaluated at Y (fEvalX off)          */
+#define SPORCO_AMD_RPCA_V_S 2    /* ... of S alone: the stateless prox_nuclear / norm_nuclear                */
+typedef struct {
+    double rho, lmbda, rlx;
+    double u_scale;           /* pending U /= rsf (admm.py:573): gram and iter apply it, iter stores U with it */
+} sporco_amd_rpca_params;
+int sporco_amd_rpca_create(int dtype, int32_t R, int32_t C, int device, void *stream, sporco_amd_rpca_t *out);
+int sporco_amd_rpca_destroy(sporco_amd_rpca_t h);
+int sporco_amd_rpca_sync(sporco_amd_rpca_t h);
+/* out[0] = positions of the long axis staged per step of rpca_gram, out[1] = positions of a slab, out[2] = slabs,
+ * out[3] = 64 x 64 blocks a side of G, out[4] = positions of a block of rpca_iter, out[5] = its workgroups,
+ * out[6], out[7] = 1 where rpca_gram / rpca_iter use a matrix instruction, out[8], out[9] = bytes of LDS of a
+ * workgroup of rpca_gram and of rpca_iter. */
+int sporco_amd_rpca_plan(sporco_amd_rpca_t h, int64_t out[10]);
+/* S (R, C) in the handle's precision.  on_device: a device pointer that is read in place, not copied; it stays
+ * valid and unchanged until the next set_signal or the handle's end.  Forms ||S||^2 (OUT_C2 of every later out). */
+int sporco_amd_rpca_set_signal(sporco_amd_rpca_t h, const void *S, int on_device);
+/* Copy a host (R, C) array in or out. */
+int sporco_amd_rpca_upload(sporco_amd_rpca_t h, int var, const void *src);
+int sporco_amd_rpca_download(sporco_amd_rpca_t h, int var, void *dst);
+/* *out = the device buffer of X, Y or U, valid while the handle lives. */
+int sporco_amd_rpca_devptr(sporco_amd_rpca_t h, int var, void **out);
+/* G (host, n x n doubles) <- the Gram matrix of V by `mode`: rpca_gram, rpca_gram_reduce, one download. */
+int sporco_amd_rpca_gram(sporco_amd_rpca_t h, int mode, double u_scale, double *G);
+/* One iteration after the host step.  T: host (n, n) doubles, symmetric.  out: OUT_R2 = ||X + Y - S||^2,
+ * OUT_S2 = ||Y - Yprev||^2 (rho applied by the host), OUT_AX2 = ||X||^2, OUT_Y2, OUT_U2, OUT_L1 = sum |Y|,
+ * OUT_L21 = sum |S - X| (NrmL1 with gEvalY off), OUT_C2 = ||S||^2.  U is stored with u_scale applied. */
+int sporco_amd_rpca_iter(sporco_amd_rpca_t h, const sporco_amd_rpca_params *p, const double *T,
+                         double out[SPORCO_AMD_OUT_COUNT]);
+/* X <- S T (R >= C) or T S: singular value thresholding of the signal itself.  Y and U are not touched. */
+int sporco_amd_rpca_apply(sporco_amd_rpca_t h, const double *T);
+int sporco_amd_rpca_profile(sporco_amd_rpca_t h, int enable);
+int sporco_amd_rpca_profile_read(sporco_amd_rpca_t h, int slot, const char **name, double *total_ms,
                                  int64_t *count);
 
 #ifdef __cplusplus

@@ -122,6 +122,10 @@ EXPORTS = (
     'sporco_amd_cmod_set_signal', 'sporco_amd_cmod_set_coef', 'sporco_amd_cmod_set_solve', 'sporco_amd_cmod_upload',
     'sporco_amd_cmod_download', 'sporco_amd_cmod_iter', 'sporco_amd_cmod_dfid', 'sporco_amd_cmod_profile',
     'sporco_amd_cmod_profile_read',
+    'sporco_amd_rpca_create', 'sporco_amd_rpca_destroy', 'sporco_amd_rpca_sync', 'sporco_amd_rpca_plan',
+    'sporco_amd_rpca_set_signal', 'sporco_amd_rpca_upload', 'sporco_amd_rpca_download', 'sporco_amd_rpca_devptr',
+    'sporco_amd_rpca_gram', 'sporco_amd_rpca_iter', 'sporco_amd_rpca_apply', 'sporco_amd_rpca_profile',
+    'sporco_amd_rpca_profile_read',
 )
 
 
@@ -235,6 +239,17 @@ class CmodParams(ctypes.Structure):
 
 CMOD_X, CMOD_Y, CMOD_U, CMOD_SZT, CMOD_G, CMOD_SZTD = range(6)
 CMOD_MAX_DIM = 512             # SPORCO_AMD_CMOD_MAX_DIM
+
+
+class RpcaParams(ctypes.Structure):
+    """sporco_amd_rpca_params: scalars of one RobustPCA iteration."""
+    _fields_ = [('rho', ctypes.c_double), ('lmbda', ctypes.c_double), ('rlx', ctypes.c_double),
+                ('u_scale', ctypes.c_double)]
+
+
+RPCA_X, RPCA_Y, RPCA_U = range(3)
+RPCA_V_SYU, RPCA_V_SY, RPCA_V_S = range(3)
+RPCA_MAX_DIM = 512             # SPORCO_AMD_RPCA_MAX_DIM
 
 REDUCE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
 EUNSUPPORTED = -5
@@ -496,6 +511,19 @@ def load(path=None):
         'sporco_amd_cmod_dfid': [vp, ctypes.c_int, dptr],
         'sporco_amd_cmod_profile': [vp, ctypes.c_int],
         'sporco_amd_cmod_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
+                                         ctypes.POINTER(i64)],
+        'sporco_amd_rpca_create': [ctypes.c_int, i32, i32, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_rpca_destroy': [vp], 'sporco_amd_rpca_sync': [vp],
+        'sporco_amd_rpca_plan': [vp, ctypes.POINTER(i64)],
+        'sporco_amd_rpca_set_signal': [vp, vp, ctypes.c_int],
+        'sporco_amd_rpca_upload': [vp, ctypes.c_int, vp],
+        'sporco_amd_rpca_download': [vp, ctypes.c_int, vp],
+        'sporco_amd_rpca_devptr': [vp, ctypes.c_int, ctypes.POINTER(vp)],
+        'sporco_amd_rpca_gram': [vp, ctypes.c_int, dbl, vp],
+        'sporco_amd_rpca_iter': [vp, ctypes.POINTER(RpcaParams), vp, dptr],
+        'sporco_amd_rpca_apply': [vp, vp],
+        'sporco_amd_rpca_profile': [vp, ctypes.c_int],
+        'sporco_amd_rpca_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                          ctypes.POINTER(i64)],
         'sporco_amd_spl_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                         ctypes.POINTER(i64)],
@@ -1723,6 +1751,119 @@ class CmodHandle(object):
         for slot in range(self._lib.sporco_amd_profile_slots()):
             name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
             check(self._lib.sporco_amd_cmod_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
+                                                         ctypes.byref(cnt)))
+            if cnt.value:
+                res[name.value.decode()] = (ms.value, cnt.value)
+        return res
+
+
+class RpcaHandle(object):
+    """Owner of one device-side RobustPCA problem (sporco_amd_rpca_*), also the short-lived engine of
+    ``prox.prox_nuclear`` / ``prox.norm_nuclear``: S (R, C), a host array that is copied or a
+    :class:`sporco_amd.device.DeviceArray` that is read in place (the handle keeps it alive); X / Y / U (R, C), host
+    arrays in and out, or views of the handle's buffers (:meth:`device_view`)."""
+
+    def __init__(self, R, C, dtype, device=0, stream=None):
+        self.dims = (int(R), int(C))
+        self.n = min(self.dims)
+        self.dtype = np.dtype(dtype)
+        h = ctypes.c_void_p()
+        check(lib().sporco_amd_rpca_create(dtype_code(dtype), int(R), int(C), int(device),
+                                           ctypes.c_void_p(stream or 0), ctypes.byref(h)))
+        self._h = h
+        self._lib = lib()
+        self._keep = None
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sporco_amd_rpca_destroy(self._h)
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        check(self._lib.sporco_amd_rpca_sync(self._h))
+
+    def plan(self):
+        """``dict(KS, slab, slabs, blocks, KB, workgroups, mfma_gram, mfma_iter, lds_gram, lds_iter)``: the positions
+        of the long axis staged per step of rpca_gram, those of a slab, the slabs, the 64 x 64 blocks a side of the
+        Gram matrix, the positions of a block of rpca_iter and its workgroups, whether the two kernels use a matrix
+        instruction, the bytes of LDS of a workgroup of each."""
+        out = (ctypes.c_int64 * 10)()
+        check(self._lib.sporco_amd_rpca_plan(self._h, out))
+        return dict(zip(('KS', 'slab', 'slabs', 'blocks', 'KB', 'workgroups', 'mfma_gram', 'mfma_iter', 'lds_gram',
+                         'lds_iter'), (int(v) for v in out)))
+
+    def set_signal(self, S):
+        if isinstance(S, np.ndarray):
+            S = _carr(S, self.dtype)
+            if S.shape != self.dims:
+                raise ValueError("array of shape %s where %s is expected" % (S.shape, self.dims))
+            check(self._lib.sporco_amd_rpca_set_signal(self._h, _ptr(S), 0))
+            self._keep = None
+            return
+        if tuple(S.shape) != self.dims or S.dtype != self.dtype:
+            raise ValueError("device array of shape %s and dtype %s where %s, %s is expected"
+                             % (tuple(S.shape), S.dtype, self.dims, self.dtype))
+        check(self._lib.sporco_amd_rpca_set_signal(self._h, ctypes.c_void_p(S.ptr), 1))
+        self._keep = S
+
+    def upload(self, var, a):
+        a = _carr(a, self.dtype)
+        if a.shape != self.dims:
+            raise ValueError("array of shape %s where %s is expected" % (a.shape, self.dims))
+        check(self._lib.sporco_amd_rpca_upload(self._h, int(var), _ptr(a)))
+
+    def download(self, var):
+        out = np.empty(self.dims, dtype=self.dtype)
+        check(self._lib.sporco_amd_rpca_download(self._h, int(var), _ptr(out)))
+        return out
+
+    def device_view(self, var):
+        """A :class:`sporco_amd.device.DeviceArray` over the buffer of X, Y or U: no copy, and the view keeps this
+        handle alive.  It shows whatever the handle's calls leave in the buffer."""
+        from .device import DeviceArray
+        p = ctypes.c_void_p()
+        check(self._lib.sporco_amd_rpca_devptr(self._h, int(var), ctypes.byref(p)))
+        return DeviceArray(self.dims, self.dtype, ptr=p.value, base=self)
+
+    def gram(self, mode, u_scale=1.0):
+        """The (n, n) float64 Gram matrix of V by ``mode`` (RPCA_V_*), n = min(R, C)."""
+        G = np.empty((self.n, self.n), dtype=np.float64)
+        check(self._lib.sporco_amd_rpca_gram(self._h, int(mode), float(u_scale), _ptr(G)))
+        return G
+
+    def _t(self, T):
+        T = _carr(T, np.float64)
+        if T.shape != (self.n, self.n):
+            raise ValueError("T of shape %s where %s is expected" % (T.shape, (self.n, self.n)))
+        return T
+
+    def iter(self, params, T):
+        T = self._t(T)
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_rpca_iter(self._h, ctypes.byref(params), _ptr(T), out))
+        return list(out)
+
+    def apply(self, T):
+        """X <- S T (R >= C) or T S."""
+        T = self._t(T)
+        check(self._lib.sporco_amd_rpca_apply(self._h, _ptr(T)))
+
+    def profile(self, enable):
+        check(self._lib.sporco_amd_rpca_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self):
+        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
+        res = {}
+        for slot in range(self._lib.sporco_amd_profile_slots()):
+            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
+            check(self._lib.sporco_amd_rpca_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
                                                          ctypes.byref(cnt)))
             if cnt.value:
                 res[name.value.decode()] = (ms.value, cnt.value)

@@ -1475,4 +1475,133 @@ int sporco_amd_cmod_profile_read(sporco_amd_cmod_t h, int slot, const char **nam
     SA_API_END
 }
 
+// ---- RobustPCA / prox_nuclear: a handle of its own (csc_impl.h RpcaBase) --------------------------------------
+#define SA_RPCA_HANDLE(h)                                                              \
+    SA_REQUIRE((h) != nullptr && (h)->impl, "null rpca handle");                       \
+    SA_HIP(hipSetDevice((h)->device));
+
+int sporco_amd_rpca_create(int dtype, int32_t R, int32_t C, int device, void *stream, sporco_amd_rpca_t *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out != nullptr, "null argument");
+    SA_REQUIRE(R >= 1 && C >= 1, "rpca: R >= 1, C >= 1");
+    static_assert(SPORCO_AMD_RPCA_MAX_DIM == kRpcaMaxDim, "one limit for the rpca handle");
+    SA_REQUIRE((R < C ? R : C) <= SPORCO_AMD_RPCA_MAX_DIM, "rpca: the kernels serve arrays whose short side is at most 512");
+    SA_REQUIRE((int64_t)R * C < ((int64_t)1 << 31), "rpca: fewer than 2^31 elements");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    std::unique_ptr<sporco_amd_rpca> h(new sporco_amd_rpca);
+    h->device = device;
+    h->impl.reset(make_rpca(dtype, R, C, device, stream));
+    *out = h.release();
+    SA_API_END
+}
+
+int sporco_amd_rpca_destroy(sporco_amd_rpca_t h) {
+    SA_API_BEGIN
+    if (h) {
+        (void)hipSetDevice(h->device);
+        delete h;
+    }
+    SA_API_END
+}
+
+int sporco_amd_rpca_sync(sporco_amd_rpca_t h) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    h->impl->sync();
+    SA_API_END
+}
+
+int sporco_amd_rpca_plan(sporco_amd_rpca_t h, int64_t out[10]) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    h->impl->plan(out);
+    SA_API_END
+}
+
+int sporco_amd_rpca_set_signal(sporco_amd_rpca_t h, const void *S, int on_device) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    h->impl->set_signal(S, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_rpca_upload(sporco_amd_rpca_t h, int var, const void *src) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    h->impl->upload(var, src);
+    SA_API_END
+}
+
+int sporco_amd_rpca_download(sporco_amd_rpca_t h, int var, void *dst) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    h->impl->download(var, dst);
+    SA_API_END
+}
+
+int sporco_amd_rpca_devptr(sporco_amd_rpca_t h, int var, void **out) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    SA_REQUIRE(out != nullptr, "null argument");
+    *out = h->impl->var_ptr(var);
+    SA_API_END
+}
+
+int sporco_amd_rpca_gram(sporco_amd_rpca_t h, int mode, double u_scale, double *G) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    h->impl->gram(mode, u_scale, G);
+    SA_API_END
+}
+
+int sporco_amd_rpca_iter(sporco_amd_rpca_t h, const sporco_amd_rpca_params *p, const double *T,
+                         double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
+    h->impl->iter(*p, T, out);
+    SA_API_END
+}
+
+int sporco_amd_rpca_apply(sporco_amd_rpca_t h, const double *T) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    h->impl->apply(T);
+    SA_API_END
+}
+
+int sporco_amd_rpca_profile(sporco_amd_rpca_t h, int enable) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    h->impl->sync();
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (enable)
+        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
+            hipEvent_t e;
+            SA_HIP(hipEventCreate(&e));
+            pr.pool.push_back(e);
+        }
+    pr.on = enable != 0;
+    SA_API_END
+}
+
+int sporco_amd_rpca_profile_read(sporco_amd_rpca_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
+    SA_API_BEGIN
+    SA_RPCA_HANDLE(h);
+    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
+    Profiler &pr = h->impl->prof;
+    pr.drain();
+    if (name) *name = kProfNames[slot];
+    if (total_ms) *total_ms = pr.total_ms[slot];
+    if (launches) *launches = pr.count[slot];
+    pr.total_ms[slot] = 0.0;
+    pr.count[slot] = 0;
+    SA_API_END
+}
+
 }  // extern "C"

@@ -43,7 +43,8 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "bpdn_dts",         "bpdn_iter",        "bpdn_joint_rows",
                                     "bpdn_joint_apply", "bpdn_lsc",
                                     "cmod_gram",        "cmod_gram_reduce", "cmod_rhs",
-                                    "cmod_iter",        "cmod_dfid"};
+                                    "cmod_iter",        "cmod_dfid",        "rpca_gram",
+                                    "rpca_gram_reduce", "rpca_iter"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
 // normal use).  Read ONCE, when a handle is made -- except SPORCO_AMD_HOST_LOOP and
@@ -662,6 +663,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_spline.inc"
 #include "api_bpdn.inc"
 #include "api_cmod.inc"
+#include "api_rpca.inc"
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {
     if (dims.dtype == SPORCO_AMD_F32) return new Csc<float>(dims, device, stream, dict_channels, depth);

@@ -31,6 +31,7 @@
 #include "csc_spline.h"
 #include "csc_bpdn.h"
 #include "csc_cmod.h"
+#include "csc_rpca.h"
 #include "fft.h"
 
 #include <atomic>
@@ -140,6 +141,9 @@ enum ProfSlot {
     PS_CMOD_RHS,                // ... the right-hand side of the x step
     PS_CMOD_ITER,               // ... the whole iteration of a block of 16 dictionary columns
     PS_CMOD_DFID,               // ... sum (F Z - S)^2
+    PS_RPCA_GRAM,               // RobustPCA / prox_nuclear: the slab partials of the Gram matrix of V (csc_rpca.h)
+    PS_RPCA_GRAM_REDUCE,        // ... added in slab order
+    PS_RPCA_ITER,               // ... X = V T, relax, y step, u step, sums (apply: X alone)
     PS_COUNT
 };
 extern const char *kProfNames[PS_COUNT];
@@ -418,6 +422,23 @@ struct CmodBase {
 };
 CmodBase *make_cmod(int dtype, int N, int M, int64_t K, int device, void *stream);
 
+// The handle of RobustPCA and of the stateless prox_nuclear / norm_nuclear (api_rpca.inc): X, Y, U of one (R, C)
+// problem as NumPy has them, its own or a borrowed S, the Gram matrix and its slab partials, T, and a stream.
+struct RpcaBase {
+    virtual ~RpcaBase() {}
+    virtual void sync() = 0;
+    virtual void plan(int64_t out[10]) = 0;
+    virtual void set_signal(const void *S, bool on_device) = 0;
+    virtual void upload(int var, const void *src) = 0;
+    virtual void download(int var, void *dst) = 0;
+    virtual void *var_ptr(int var) = 0;
+    virtual void gram(int mode, double u_scale, double *G_host) = 0;
+    virtual void iter(const sporco_amd_rpca_params &p, const double *T_host, double *out_host) = 0;
+    virtual void apply(const double *T_host) = 0;
+    Profiler prof;
+};
+RpcaBase *make_rpca(int dtype, int R, int C, int device, void *stream);
+
 // the one place that instantiates Csc<float> / Csc<double> (csc_api.hip)
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream,
                   int depth = 1);
@@ -457,6 +478,11 @@ struct sporco_amd_bpdn {
 
 struct sporco_amd_cmod {
     std::unique_ptr<sporco_amd::CmodBase> impl;
+    int device;
+};
+
+struct sporco_amd_rpca {
+    std::unique_ptr<sporco_amd::RpcaBase> impl;
     int device;
 };
 

@@ -108,6 +108,14 @@ __device__ __forceinline__ void sa_stream_store4(float *p, const float (&v)[4]) 
 __device__ __forceinline__ sa_floatx4 sa_mfma_f32_16x16x4(float a, float b, sa_floatx4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
+// The same product with float64 operands and sums (v_mfma_f64_16x16x4_f64): a and b as above, one double a lane.
+// The C / D map is NOT that of the float32 form: lane l holds rows (l >> 4) + 4 r, r = 0..3, of column l & 15.
+// How the four products of a step are rounded into the sum is not documented; csc_rpca.h promises no bit equality
+// with an fma chain.
+typedef double sa_doublex4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ sa_doublex4 sa_mfma_f64_16x16x4(double a, double b, sa_doublex4 c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
 
 // Wave-uniform loads of read-only data through the scalar cache (s_load_dword[x2]):
 // the pointer is re-typed to the constant address space, which is what lets the

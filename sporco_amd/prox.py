@@ -4,6 +4,10 @@
 (sporco/prox/_l21.py:51-88), ``proj_l2`` (sporco/prox/_lp.py:334-340) and
 ``proj_l1`` (sporco/prox/_l1proj.py:24-154) for real arrays and scalar parameters; inside the solvers the same arithmetic runs
 fused into the ADMM / PGM epilogue kernels, where weight arrays are supported.
+
+``prox_nuclear`` and ``norm_nuclear`` (sporco/prox/_nuclear.py) for real float32 / float64 2-D arrays whose short
+side is at most 512, host arrays or :class:`sporco_amd.device.DeviceArray`: the device forms the Gram matrix of the
+short side in double (csrc/csc_rpca.h), the host its eigendecomposition, the device the product.  No SVD is taken.
 """
 
 import numpy as np
@@ -160,3 +164,69 @@ def proj_l1(v, gamma, axis=None):
 
 def norm_l1(x, axis=None):
     return np.sum(np.abs(x), axis=axis, keepdims=axis is not None)
+
+
+def svt_matrix(G, alpha):
+    """The host step of singular value thresholding.  ``G``: the (n, n) Gram matrix of the short side of ``V``, ``G
+    = W diag(sigma^2) W^T``.  Returns ``(T, sigma, ss)`` in float64, singular values descending: ``ss = max(0, sigma
+    - alpha)`` and ``T = W diag(ss / sigma) W^T``, so that ``prox_nuclear(V, alpha) = V T`` (or ``T V`` for a wide
+    ``V``).  Directions with ``sigma <= alpha`` get the factor 0, and the factor is continuous there."""
+    G = np.asarray(G, dtype=np.float64)
+    w, W = np.linalg.eigh(0.5 * (G + G.T))
+    sigma = np.sqrt(np.maximum(w, 0.0))[::-1]
+    W = W[:, ::-1]
+    ss = np.maximum(0.0, sigma - float(alpha))
+    f = np.zeros_like(sigma)
+    nz = sigma > 0.0
+    f[nz] = ss[nz] / sigma[nz]
+    return (W * f).dot(W.T), sigma, ss
+
+
+def _nuclear_handle(v, name):
+    """What is refused of the argument, then a handle with the argument as its signal."""
+    from .device import is_device_array
+    if not is_device_array(v):
+        v = np.asarray(v)
+        if np.iscomplexobj(v) or v.dtype not in (np.float32, np.float64):
+            raise TypeError("%s works on real float32 or float64 arrays, not %s" % (name, v.dtype))
+    if len(v.shape) != 2:
+        raise ValueError("%s takes an array of two axes" % name)
+    if min(v.shape) < 1:
+        raise ValueError("%s: empty array" % name)
+    if min(v.shape) > _lib.RPCA_MAX_DIM:
+        raise ValueError("%s: an array of shape %s; the kernels serve a short side of up to %d"
+                         % (name, tuple(v.shape), _lib.RPCA_MAX_DIM))
+    h = _lib.RpcaHandle(v.shape[0], v.shape[1], v.dtype)
+    h.set_signal(v if is_device_array(v) else np.ascontiguousarray(v))
+    return h, is_device_array(v)
+
+
+def norm_nuclear(x):
+    """The nuclear norm of a 2-D array, the sum of its singular values (sporco/prox/_nuclear.py:21-41): the square
+    roots of the eigenvalues of the Gram matrix of its short side, which the device forms in double."""
+    h, _ = _nuclear_handle(x, 'norm_nuclear')
+    try:
+        G = h.gram(_lib.RPCA_V_S)
+    finally:
+        h.close()
+    return float(np.sum(np.sqrt(np.maximum(np.linalg.eigvalsh(0.5 * (G + G.T)), 0.0))))
+
+
+def prox_nuclear(v, alpha):
+    """Singular value thresholding (sporco/prox/_nuclear.py:45-67): returns ``(X, ss)``, ``X`` of the kind and dtype
+    of ``v`` (a returned :class:`sporco_amd.device.DeviceArray` keeps its short-lived handle alive) and ``ss`` the
+    thresholded singular values, float64, descending, of length ``min(v.shape)``."""
+    if np.ndim(alpha) != 0 or not float(alpha) >= 0.0:
+        raise ValueError("alpha is a scalar that is not negative")
+    h, on_device = _nuclear_handle(v, 'prox_nuclear')
+    try:
+        T, _, ss = svt_matrix(h.gram(_lib.RPCA_V_S), alpha)
+        h.apply(T)
+        if on_device:
+            return h.device_view(_lib.RPCA_X), ss
+        x = h.download(_lib.RPCA_X)
+    except Exception:
+        h.close()
+        raise
+    h.close()
+    return x, ss
