@@ -1304,6 +1304,68 @@ int sporco_amd_bpdn_profile_read(sporco_amd_bpdn_t h, int slot, const char **nam
  * lets another handle read the coefficients in place (sporco_amd_cmod_set_coef with on_device). */
 int sporco_amd_bpdn_devptr(sporco_amd_bpdn_t h, int var, void **out);
 
+/* ---- dense sparse coding by proximal gradient steps: sporco.pgm.bpdn BPDN / WeightedBPDN
+ * (sporco/pgm/bpdn.py:26-375) ----
+ *     minimise (1/2) ||D x - s||^2_W + lmbda ||wl1 x||_1,   W = diag(w).
+ * A handle of sporco_amd_bpdn_pgm_create is a bpdn handle (sync, plan, set_dict, upload, download, profile,
+ * devptr and destroy are those above; D^T S is formed as there, there is no solve matrix and no sporco_amd_bpdn_iter)
+ * with the arrays of the iteration: two X arrays (the iterate and the one before; `advance` swaps their roles),
+ * two Y arrays (the second for the robust backtracking rule), G, Z, ZZ, all (M, K), and the weight w (N, K).
+ * One call of sporco_amd_bpdn_pgm_step launches the phases it is asked for (csrc/csc_pgm_bpdn.h) and the
+ * fixed-order reduction; both phases in one call are a whole step X' = prox(Y - G / L) with every scalar of
+ * F, Q_L, Rsdl, DFid and RegL1.  All arrays start at zero. */
+#define SPORCO_AMD_BPDN_XPRV 6  /* (M,K)  the iterate before X                                                 */
+#define SPORCO_AMD_BPDN_YPRV 7  /* (M,K)  robust rule: the Y of the iteration before                           */
+#define SPORCO_AMD_BPDN_G 8     /* (M,K)  the gradient D^T W (D Y - S) of the last gradient phase              */
+#define SPORCO_AMD_BPDN_Z 9     /* (M,K)  robust rule: Z                                                       */
+#define SPORCO_AMD_BPDN_ZZ 10   /* (M,K)  Monotone: the X' of the last step before a revert                    */
+#define SPORCO_AMD_BPDN_W 11    /* (N,K)  weight array of the data fidelity term (upload NULL: the scalar w)   */
+#define SPORCO_AMD_PGMB_PHASE_GRAD 1
+#define SPORCO_AMD_PGMB_PHASE_PROX 2
+#define SPORCO_AMD_PGMB_Y_LOAD 0      /* Y as it stands                                                        */
+#define SPORCO_AMD_PGMB_Y_MOMENTUM 1  /* Y = Xprv + beta (Xprv - Xold), formed on the way in and stored        */
+#define SPORCO_AMD_PGMB_Y_ROBUST 2    /* [Z += zc (Xprv - Yprv);] Y = (tk Xprv + t Z) / (tk + t), stored       */
+/* out[] of sporco_amd_bpdn_pgm_step (the halves applied) */
+#define SPORCO_AMD_PGMB_FY 0    /* f(Y) = (1/2) sum w (D Y - S)^2        (gradient phase)                      */
+#define SPORCO_AMD_PGMB_FX 1    /* f(X')                                  (prox phase)                          */
+#define SPORCO_AMD_PGMB_DXG 2   /* <X' - Y, G>                                                                 */
+#define SPORCO_AMD_PGMB_DXY2 3  /* ||X' - Y||^2                                                                */
+#define SPORCO_AMD_PGMB_L1 4    /* ||wl1 X'||_1                                                                */
+#define SPORCO_AMD_PGMB_X2 5    /* ||X'||^2                                                                    */
+#define SPORCO_AMD_PGMB_RS2 6   /* ||X' - Yprv||^2 (Yprv: Y where the Y arrays were not swapped);
+                                   sporco_amd_bpdn_pgm_ystep: ||X - Y||^2                                      */
+#define SPORCO_AMD_PGMB_G2 7    /* ||G||^2                                (gradient phase)                      */
+#define SPORCO_AMD_PGMB_DG2 8   /* ||D G||^2                              (gradient phase alone, cauchy)        */
+#define SPORCO_AMD_PGMB_BBXG 9  /* <Xprv - Xold, G - Gold>                (gradient phase, bb)                  */
+#define SPORCO_AMD_PGMB_BBG2 10 /* ||G - Gold||^2                                                              */
+typedef struct {
+    double L, lmbda;
+    double wl1, w;            /* the scalar weights, read where no array is set                              */
+    double beta;              /* Y_MOMENTUM                                                                  */
+    double tk, t, zc;         /* Y_ROBUST                                                                    */
+    int32_t phase;            /* SPORCO_AMD_PGMB_PHASE_GRAD | _PROX                                          */
+    int32_t ymode;            /* SPORCO_AMD_PGMB_Y_* (gradient phase)                                        */
+    int32_t advance;          /* first: X becomes Xprv and the array of the iterate before it receives X'    */
+    int32_t advance_y;        /* ... and Y becomes Yprv (the robust rule)                                    */
+    int32_t nonneg;           /* NonNegCoef                                                                  */
+    int32_t revert;           /* prox phase: X' = Xprv (Monotone's revert) with the sums of that X'          */
+    int32_t z_update;         /* Y_ROBUST: apply zc first                                                    */
+    int32_t cauchy;           /* gradient phase alone: form OUT DG2                                          */
+    int32_t bb;               /* gradient phase: form BBXG, BBG2 against the G of the gradient phase before  */
+    int32_t keep_zz;          /* prox phase: also store X' to ZZ                                             */
+    int32_t reserved[2];
+} sporco_amd_bpdn_pgm_params;
+int sporco_amd_bpdn_pgm_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream,
+                               sporco_amd_bpdn_t *out);
+/* out == NULL: no reduction is read back (the launches are queued and the call returns). */
+int sporco_amd_bpdn_pgm_step(sporco_amd_bpdn_t h, const sporco_amd_bpdn_pgm_params *p, double out[SPORCO_AMD_OUT_COUNT]);
+/* Y = X + gamma (ZZ - X) + beta (X - Xprv) (use_zz == 0: without the ZZ term), written to the other Y array with
+ * advance_y (Y becomes Yprv first); out[SPORCO_AMD_PGMB_RS2] = ||X - Y||^2, out == NULL as above. */
+int sporco_amd_bpdn_pgm_ystep(sporco_amd_bpdn_t h, double beta, double gamma, int use_zz, int advance_y,
+                              double out[SPORCO_AMD_OUT_COUNT]);
+/* variable dst <- variable src on the device, both (M,K). */
+int sporco_amd_bpdn_pgm_copy(sporco_amd_bpdn_t h, int dst, int src);
+
 /* ---- dense dictionary update: sporco.admm.cmod CnstrMOD (sporco/admm/cmod.py:21-342) ----
  *     minimise ||D Z - S||^2  such that  ||d_m|| = 1 [, mean(d_m) = 0]   on  d = g,
  * Z (M, K), S (N, K), X / Y / U (N, M), every array row-major as NumPy has it.  set_coef forms Z Z^T and S Z^T on

@@ -118,6 +118,7 @@ EXPORTS = (
     'sporco_amd_bpdn_create', 'sporco_amd_bpdn_destroy', 'sporco_amd_bpdn_sync', 'sporco_amd_bpdn_plan',
     'sporco_amd_bpdn_set_dict', 'sporco_amd_bpdn_set_solve', 'sporco_amd_bpdn_upload', 'sporco_amd_bpdn_download',
     'sporco_amd_bpdn_iter', 'sporco_amd_bpdn_profile', 'sporco_amd_bpdn_profile_read', 'sporco_amd_bpdn_devptr',
+    'sporco_amd_bpdn_pgm_create', 'sporco_amd_bpdn_pgm_step', 'sporco_amd_bpdn_pgm_ystep', 'sporco_amd_bpdn_pgm_copy',
     'sporco_amd_cmod_create', 'sporco_amd_cmod_destroy', 'sporco_amd_cmod_sync', 'sporco_amd_cmod_plan',
     'sporco_amd_cmod_set_signal', 'sporco_amd_cmod_set_coef', 'sporco_amd_cmod_set_solve', 'sporco_amd_cmod_upload',
     'sporco_amd_cmod_download', 'sporco_amd_cmod_iter', 'sporco_amd_cmod_dfid', 'sporco_amd_cmod_profile',
@@ -228,6 +229,24 @@ class BpdnParams(ctypes.Structure):
 
 BPDN_S, BPDN_X, BPDN_Y, BPDN_U, BPDN_WL1, BPDN_DTS = range(6)
 BPDN_MAX_DIM = 512
+
+
+class BpdnPgmParams(ctypes.Structure):
+    """sporco_amd_bpdn_pgm_params: scalars and phases of one proximal gradient step of pgm.bpdn."""
+    _fields_ = [('L', ctypes.c_double), ('lmbda', ctypes.c_double), ('wl1', ctypes.c_double), ('w', ctypes.c_double),
+                ('beta', ctypes.c_double), ('tk', ctypes.c_double), ('t', ctypes.c_double), ('zc', ctypes.c_double),
+                ('phase', ctypes.c_int32), ('ymode', ctypes.c_int32), ('advance', ctypes.c_int32),
+                ('advance_y', ctypes.c_int32), ('nonneg', ctypes.c_int32), ('revert', ctypes.c_int32),
+                ('z_update', ctypes.c_int32), ('cauchy', ctypes.c_int32), ('bb', ctypes.c_int32),
+                ('keep_zz', ctypes.c_int32), ('reserved', ctypes.c_int32 * 2)]
+
+
+# the arrays a handle of sporco_amd_bpdn_pgm_create adds, its phases, Y modes and out[] slots (SPORCO_AMD_PGMB_*)
+BPDN_XPRV, BPDN_YPRV, BPDN_G, BPDN_Z, BPDN_ZZ, BPDN_W = range(6, 12)
+PGMB_PHASE_GRAD, PGMB_PHASE_PROX = 1, 2
+PGMB_Y_LOAD, PGMB_Y_MOMENTUM, PGMB_Y_ROBUST = range(3)
+(PGMB_FY, PGMB_FX, PGMB_DXG, PGMB_DXY2, PGMB_L1, PGMB_X2, PGMB_RS2, PGMB_G2, PGMB_DG2, PGMB_BBXG,
+ PGMB_BBG2) = range(11)
 
 
 class CmodParams(ctypes.Structure):
@@ -500,6 +519,10 @@ def load(path=None):
         'sporco_amd_bpdn_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                          ctypes.POINTER(i64)],
         'sporco_amd_bpdn_devptr': [vp, ctypes.c_int, ctypes.POINTER(vp)],
+        'sporco_amd_bpdn_pgm_create': [ctypes.c_int, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_bpdn_pgm_step': [vp, ctypes.POINTER(BpdnPgmParams), dptr],
+        'sporco_amd_bpdn_pgm_ystep': [vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, dptr],
+        'sporco_amd_bpdn_pgm_copy': [vp, ctypes.c_int, ctypes.c_int],
         'sporco_amd_cmod_create': [ctypes.c_int, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
         'sporco_amd_cmod_destroy': [vp], 'sporco_amd_cmod_sync': [vp],
         'sporco_amd_cmod_plan': [vp, ctypes.POINTER(i64)],
@@ -1551,11 +1574,13 @@ class BpdnHandle(object):
     """Owner of one device-side BPDN / BPDNJoint / ElasticNet problem (sporco_amd_bpdn_*): D (N, M), S (N, K),
     X / Y / U (M, K), host arrays in and out."""
 
+    _create = 'sporco_amd_bpdn_create'
+
     def __init__(self, N, M, K, dtype, device=0, stream=None):
         self.dims = (int(N), int(M), int(K))
         self.dtype = np.dtype(dtype)
         h = ctypes.c_void_p()
-        check(lib().sporco_amd_bpdn_create(dtype_code(dtype), int(N), int(M), int(K), int(device),
+        check(getattr(lib(), self._create)(dtype_code(dtype), int(N), int(M), int(K), int(device),
                                            ctypes.c_void_p(stream or 0), ctypes.byref(h)))
         self._h = h
         self._lib = lib()
@@ -1583,7 +1608,7 @@ class BpdnHandle(object):
 
     def _shape(self, var):
         N, M, K = self.dims
-        return (N, K) if var == BPDN_S else (M, K)
+        return (N, K) if var in (BPDN_S, BPDN_W) else (M, K)
 
     def set_dict(self, D):
         D = _carr(D, self.dtype)
@@ -1644,6 +1669,33 @@ class BpdnHandle(object):
             if cnt.value:
                 res[name.value.decode()] = (ms.value, cnt.value)
         return res
+
+
+class PgmBpdnHandle(BpdnHandle):
+    """Owner of one device-side pgm.bpdn BPDN / WeightedBPDN problem (sporco_amd_bpdn_pgm_*): a
+    :class:`BpdnHandle` with the arrays of the proximal gradient iteration (``BPDN_XPRV`` ... ``BPDN_W``)."""
+
+    _create = 'sporco_amd_bpdn_pgm_create'
+
+    def step(self, params, read=True):
+        """The phases ``params`` asks for and the reduction; the ``PGMB_*`` sums, or None without ``read``."""
+        if not read:
+            check(self._lib.sporco_amd_bpdn_pgm_step(self._h, ctypes.byref(params), None))
+            return None
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_bpdn_pgm_step(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def ystep(self, beta, gamma=0.0, use_zz=False, advance_y=False, read=True):
+        """``Y = X + gamma (ZZ - X) + beta (X - Xprv)`` as a launch of its own, into the other Y array with
+        ``advance_y``; ``out[PGMB_RS2] = ||X - Y||^2``, or None without ``read``."""
+        out = (ctypes.c_double * OUT_COUNT)() if read else None
+        check(self._lib.sporco_amd_bpdn_pgm_ystep(self._h, float(beta), float(gamma), int(bool(use_zz)),
+                                                  int(bool(advance_y)), out))
+        return list(out) if read else None
+
+    def copy(self, dst, src):
+        check(self._lib.sporco_amd_bpdn_pgm_copy(self._h, int(dst), int(src)))
 
 
 class CmodHandle(object):

@@ -135,7 +135,7 @@ template <typename T> struct Bpdn : BpdnBase {
         have_p = true;
     }
 
-    T *var_buf(int var) {
+    virtual T *var_buf(int var) {
         switch (var) {
         case SPORCO_AMD_BPDN_S: return s;
         case SPORCO_AMD_BPDN_X: return x;
@@ -147,7 +147,7 @@ template <typename T> struct Bpdn : BpdnBase {
         }
     }
     void *var_ptr(int var) override { return var_buf(var); }
-    size_t var_bytes(int var) const { return sizeof(T) * (size_t)(var == SPORCO_AMD_BPDN_S ? N : M) * K; }
+    virtual size_t var_bytes(int var) const { return sizeof(T) * (size_t)(var == SPORCO_AMD_BPDN_S ? N : M) * K; }
     void upload(int var, const void *src) override {
         // (X and D^T S are results: setting them only prefills what the next iteration / set_dict overwrites)
         if (var == SPORCO_AMD_BPDN_WL1) {

@@ -1346,6 +1346,48 @@ int sporco_amd_bpdn_devptr(sporco_amd_bpdn_t h, int var, void **out) {
     SA_API_END
 }
 
+// ---- pgm.bpdn BPDN / WeightedBPDN: a bpdn handle with the arrays of the proximal gradient iteration --------------
+int sporco_amd_bpdn_pgm_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_bpdn_t *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out != nullptr, "null argument");
+    SA_REQUIRE(N >= 1 && M >= 1 && K >= 1, "bpdn: N >= 1, M >= 1, K >= 1");
+    SA_REQUIRE(N <= SPORCO_AMD_BPDN_MAX_DIM && M <= SPORCO_AMD_BPDN_MAX_DIM,
+               "bpdn: the kernels serve dictionaries of up to 512 rows and 512 columns");
+    SA_REQUIRE(K < ((int64_t)1 << 31), "bpdn: fewer than 2^31 signals");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    std::unique_ptr<sporco_amd_bpdn> h(new sporco_amd_bpdn);
+    h->device = device;
+    h->impl.reset(make_pgm_bpdn(dtype, N, M, K, device, stream));
+    *out = h.release();
+    SA_API_END
+}
+
+int sporco_amd_bpdn_pgm_step(sporco_amd_bpdn_t h, const sporco_amd_bpdn_pgm_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_BPDN_HANDLE(h);
+    SA_REQUIRE(p != nullptr, "null argument");
+    h->impl->pgm_step(*p, out);
+    SA_API_END
+}
+
+int sporco_amd_bpdn_pgm_ystep(sporco_amd_bpdn_t h, double beta, double gamma, int use_zz, int advance_y,
+                              double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_BPDN_HANDLE(h);
+    h->impl->pgm_ystep(beta, gamma, use_zz, advance_y, out);
+    SA_API_END
+}
+
+int sporco_amd_bpdn_pgm_copy(sporco_amd_bpdn_t h, int dst, int src) {
+    SA_API_BEGIN
+    SA_BPDN_HANDLE(h);
+    h->impl->pgm_copy(dst, src);
+    SA_API_END
+}
+
 // ---- CnstrMOD: a handle of its own (csc_impl.h CmodBase) ----------------------------------------------------
 #define SA_CMOD_HANDLE(h)                                                              \
     SA_REQUIRE((h) != nullptr && (h)->impl, "null cmod handle");                       \

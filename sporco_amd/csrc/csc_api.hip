@@ -42,6 +42,7 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "spl_ystep",
                                     "bpdn_dts",         "bpdn_iter",        "bpdn_joint_rows",
                                     "bpdn_joint_apply", "bpdn_lsc",
+                                    "bpdn_pgm_step",    "bpdn_pgm_ystep",
                                     "cmod_gram",        "cmod_gram_reduce", "cmod_rhs",
                                     "cmod_iter",        "cmod_dfid",        "rpca_gram",
                                     "rpca_gram_reduce", "rpca_iter"};
@@ -662,6 +663,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_tvdc.inc"
 #include "api_spline.inc"
 #include "api_bpdn.inc"
+#include "api_pgm_bpdn.inc"
 #include "api_cmod.inc"
 #include "api_rpca.inc"
 

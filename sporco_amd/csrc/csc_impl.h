@@ -30,6 +30,7 @@
 #include "csc_tvdc.h"
 #include "csc_spline.h"
 #include "csc_bpdn.h"
+#include "csc_pgm_bpdn.h"
 #include "csc_cmod.h"
 #include "csc_rpca.h"
 #include "fft.h"
@@ -136,6 +137,8 @@ enum ProfSlot {
     PS_BPDN_JOINT_ROWS,         // ... joint: the fixed-order row reductions
     PS_BPDN_JOINT_APPLY,        // ... joint: row scaling, u step, sums
     PS_BPDN_LSC,                // ... the relative residual of the x step (LinSolveCheck)
+    PS_BPDN_PGM_STEP,           // pgm.bpdn BPDN / WeightedBPDN: the phases of a proximal gradient step (csc_pgm_bpdn.h)
+    PS_BPDN_PGM_YSTEP,          // ... the Y update as a launch of its own (Monotone)
     PS_CMOD_GRAM,               // CnstrMOD: the slab partials of [Z; S] Z^T (csc_cmod.h)
     PS_CMOD_GRAM_REDUCE,        // ... added in slab order
     PS_CMOD_RHS,                // ... the right-hand side of the x step
@@ -401,9 +404,17 @@ struct BpdnBase {
     virtual void download(int var, void *dst) = 0;
     virtual void iter(const sporco_amd_bpdn_params &p, double *out_host) = 0;
     virtual void *var_ptr(int var) = 0;      // the device buffer of a variable (nullptr: not allocated)
+    // the proximal gradient steps of pgm.bpdn (api_pgm_bpdn.inc): served by a handle of sporco_amd_bpdn_pgm_create
+    virtual void pgm_step(const sporco_amd_bpdn_pgm_params &, double *) { no_pgm(); }
+    virtual void pgm_ystep(double, double, int, int, double *) { no_pgm(); }
+    virtual void pgm_copy(int, int) { no_pgm(); }
+    [[noreturn]] static void no_pgm() {
+        throw Error(SPORCO_AMD_EINVAL, "bpdn: the handle was not made by sporco_amd_bpdn_pgm_create");
+    }
     Profiler prof;
 };
 BpdnBase *make_bpdn(int dtype, int N, int M, int64_t K, int device, void *stream);
+BpdnBase *make_pgm_bpdn(int dtype, int N, int M, int64_t K, int device, void *stream);
 
 // The handle of CnstrMOD (api_cmod.inc): the dictionary variables of one (N, M, K) problem in the order the product
 // routine reads them, the Gram matrices of the coefficients, its own or a borrowed Z and S, and a stream.

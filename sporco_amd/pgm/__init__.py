@@ -1,1 +1,3 @@
 """Solver classes mirroring the reference sub-package of the same name."""
+
+from . import bpdn  # noqa: F401

@@ -39,11 +39,12 @@ ALIASES = {
     'sporco.admm.bpdn': 'sporco_amd.admm.bpdn',
     'sporco.admm.cmod': 'sporco_amd.admm.cmod',
     'sporco.dictlrn.bpdndl': 'sporco_amd.dictlrn.bpdndl',
+    'sporco.pgm.bpdn': 'sporco_amd.pgm.bpdn',
 }
 FILES = ['admm/test_cbpdn.py', 'admm/test_ccmod.py', 'admm/test_ccmodmd.py', 'pgm/test_cbpdn.py',
          'pgm/test_ccmod.py', 'dictlrn/test_cbpdndl.py', 'dictlrn/test_cbpdndlmd.py',
          'dictlrn/test_onlinecdl.py', 'admm/test_tvl1.py', 'admm/test_tvl2.py', 'admm/test_bpdn.py',
-         'admm/test_cmod.py', 'dictlrn/test_bpdndl.py']
+         'admm/test_cmod.py', 'dictlrn/test_bpdndl.py', 'pgm/test_bpdn.py']
 
 
 def main():
