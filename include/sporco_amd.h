@@ -1416,6 +1416,64 @@ int sporco_amd_cmod_profile(sporco_amd_cmod_t h, int enable);
 int sporco_amd_cmod_profile_read(sporco_amd_cmod_t h, int slot, const char **name, double *total_ms,
                                  int64_t *count);
 
+/* ---- dense dictionary update by proximal gradient steps: sporco.pgm.cmod CnstrMOD / WeightedCnstrMOD
+ * (sporco/pgm/cmod.py:24-407) ----
+ *     minimise (1/2) ||D Z - S||^2_W  such that  ||d_m|| = 1 [, mean(d_m) = 0 | d_m >= 0],   W = diag(w).
+ * A handle of sporco_amd_cmod_pgm_create is a cmod handle (sync, plan, set_signal, set_coef, upload, download, dfid,
+ * profile and destroy are those above; set_coef forms no Gram matrix, there is no solve matrix and no
+ * sporco_amd_cmod_iter; sporco_amd_cmod_dfid takes SPORCO_AMD_CMOD_X and applies the weight) with the arrays of the
+ * iteration: two X arrays (the iterate and the one before; `advance` swaps their roles), two Y arrays (`advance_y`
+ * swaps them), G, Z, ZZ, all (N, M).  sporco_amd_cmod_plan gives out[3] = blocks of 32 rows, out[4] = 16-column tiles
+ * of G per wave, out[6], out[7] = bytes of LDS of a workgroup of cmod_pgm_grad and of cmod_pgm_prox.  One call of
+ * sporco_amd_cmod_pgm_step launches the phases it is asked for in the order of the bits below (csrc/csc_pgm_cmod.h)
+ * and, with `finalize`, the fixed-order reduction of every sum.  All arrays start at zero. */
+#define SPORCO_AMD_CMOD_XPRV 6  /* (N,M)  the iterate before X                                                 */
+#define SPORCO_AMD_CMOD_YALT 7  /* (N,M)  the other Y array: the next Y after a prox phase with write_y, the Y of
+                                          the iteration before under the robust rule                           */
+#define SPORCO_AMD_CMOD_PG 8    /* (N,M)  the gradient (w (Y Z - S)) Z^T of the last gradient phase             */
+#define SPORCO_AMD_CMOD_PZ 9    /* (N,M)  robust rule: Z                                                       */
+#define SPORCO_AMD_CMOD_ZZ 10   /* (N,M)  Monotone: the X' of the last step before a revert                    */
+#define SPORCO_AMD_PGMC_PHASE_YROBUST 1 /* [Z += zc (Xprv - Yprv);] Y = (tk Xprv + t Z) / (tk + t)             */
+#define SPORCO_AMD_PGMC_PHASE_GRAD 2    /* G from Y: cmod_pgm_grad, cmod_pgm_reduce (two launches, one pass over K) */
+#define SPORCO_AMD_PGMC_PHASE_GZ2 4     /* ||G Z||^2: cmod_dfid on G (one pass over K)                         */
+#define SPORCO_AMD_PGMC_PHASE_PROX 8    /* X' = Pcn(Y - G / L) and the next Y: cmod_pgm_prox                   */
+#define SPORCO_AMD_PGMC_PHASE_DFID 16   /* F(X'): cmod_dfid with the weight (one pass over K)                  */
+/* out[] of sporco_amd_cmod_pgm_step (the halves applied) */
+#define SPORCO_AMD_PGMC_FY 0    /* f(Y) = (1/2) sum w (Y Z - S)^2        (gradient phase)                      */
+#define SPORCO_AMD_PGMC_FX 1    /* f(X')                                  (dfid phase)                          */
+#define SPORCO_AMD_PGMC_DXG 2   /* <X' - Y, G>                            (prox phase)                          */
+#define SPORCO_AMD_PGMC_DXY2 3  /* ||X' - Y||^2                                                                */
+#define SPORCO_AMD_PGMC_CNSTR 4 /* ||Pcn(X') - X'||^2                                                          */
+#define SPORCO_AMD_PGMC_RS2 6   /* ||X' - Yprv||^2 (Yprv: Y unless yprv_alt)                                   */
+#define SPORCO_AMD_PGMC_G2 7    /* ||G||^2                                (gradient phase)                      */
+#define SPORCO_AMD_PGMC_GZ2 8   /* ||G Z||^2                              (gz2 phase)                           */
+#define SPORCO_AMD_PGMC_BBXG 9  /* <Xprv - Xold, G - Gold>                (gradient phase, bb)                  */
+#define SPORCO_AMD_PGMC_BBG2 10 /* ||G - Gold||^2                                                              */
+typedef struct {
+    double L;
+    double w;                 /* the scalar weight, read where no array is set                               */
+    double beta, gamma;       /* prox phase: Ynext = X' + gamma (ZZ - X') + beta (X' - Xprv); the gamma term
+                                 under revert only (elsewhere ZZ = X')                                       */
+    double tk, t, zc;         /* robust rule                                                                 */
+    int32_t phase;            /* SPORCO_AMD_PGMC_PHASE_*                                                     */
+    int32_t advance;          /* first: X becomes Xprv and the array of the iterate before it receives X'    */
+    int32_t advance_y;        /* ... and the Y arrays change roles                                           */
+    int32_t zero_mean, nonneg; /* the projection: ZeroMean, NonNegCoef (not both)                            */
+    int32_t revert;           /* prox phase: X' = Xprv (Monotone's revert) with the sums of that X'          */
+    int32_t z_update;         /* robust rule: apply zc first                                                 */
+    int32_t bb;               /* gradient phase: form BBXG, BBG2 against the G of the gradient phase before  */
+    int32_t keep_zz;          /* prox phase: also store X' to ZZ                                             */
+    int32_t write_y;          /* prox phase: store Ynext in the other Y array                                */
+    int32_t yprv_alt;         /* prox phase: Yprv of RS2 is the other Y array (robust rule)                  */
+    int32_t finalize;         /* reduce the sums; out == NULL: without reading them back                     */
+    int32_t rs_ynext;         /* prox phase: RS2 = ||X' - Ynext||^2 (the residual under Monotone)              */
+} sporco_amd_cmod_pgm_params;
+int sporco_amd_cmod_pgm_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream,
+                               sporco_amd_cmod_t *out);
+/* W (N, K) in the handle's precision, host or (on_device) read in place as S and Z are; NULL: the scalar w. */
+int sporco_amd_cmod_pgm_set_weight(sporco_amd_cmod_t h, const void *W, int on_device);
+int sporco_amd_cmod_pgm_step(sporco_amd_cmod_t h, const sporco_amd_cmod_pgm_params *p, double out[SPORCO_AMD_OUT_COUNT]);
+
 /* ---- robust PCA: sporco.admm.rpca RobustPCA (sporco/admm/rpca.py:23-262) and sporco.prox prox_nuclear ----
  *     minimise ||X||_* + lambda ||Y||_1  such that  X + Y = S,
  * S, X, Y, U (R, C) row-major as NumPy has them, n = min(R, C) <= SPORCO_AMD_RPCA_MAX_DIM, R C < 2^31.  The x step

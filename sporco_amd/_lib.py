@@ -123,6 +123,7 @@ EXPORTS = (
     'sporco_amd_cmod_set_signal', 'sporco_amd_cmod_set_coef', 'sporco_amd_cmod_set_solve', 'sporco_amd_cmod_upload',
     'sporco_amd_cmod_download', 'sporco_amd_cmod_iter', 'sporco_amd_cmod_dfid', 'sporco_amd_cmod_profile',
     'sporco_amd_cmod_profile_read',
+    'sporco_amd_cmod_pgm_create', 'sporco_amd_cmod_pgm_set_weight', 'sporco_amd_cmod_pgm_step',
     'sporco_amd_rpca_create', 'sporco_amd_rpca_destroy', 'sporco_amd_rpca_sync', 'sporco_amd_rpca_plan',
     'sporco_amd_rpca_set_signal', 'sporco_amd_rpca_upload', 'sporco_amd_rpca_download', 'sporco_amd_rpca_devptr',
     'sporco_amd_rpca_gram', 'sporco_amd_rpca_iter', 'sporco_amd_rpca_apply', 'sporco_amd_rpca_profile',
@@ -258,6 +259,24 @@ class CmodParams(ctypes.Structure):
 
 CMOD_X, CMOD_Y, CMOD_U, CMOD_SZT, CMOD_G, CMOD_SZTD = range(6)
 CMOD_MAX_DIM = 512             # SPORCO_AMD_CMOD_MAX_DIM
+
+
+class CmodPgmParams(ctypes.Structure):
+    """sporco_amd_cmod_pgm_params: scalars and phases of one proximal gradient step of pgm.cmod."""
+    _fields_ = [('L', ctypes.c_double), ('w', ctypes.c_double), ('beta', ctypes.c_double), ('gamma', ctypes.c_double),
+                ('tk', ctypes.c_double), ('t', ctypes.c_double), ('zc', ctypes.c_double),
+                ('phase', ctypes.c_int32), ('advance', ctypes.c_int32), ('advance_y', ctypes.c_int32),
+                ('zero_mean', ctypes.c_int32), ('nonneg', ctypes.c_int32), ('revert', ctypes.c_int32),
+                ('z_update', ctypes.c_int32), ('bb', ctypes.c_int32), ('keep_zz', ctypes.c_int32),
+                ('write_y', ctypes.c_int32), ('yprv_alt', ctypes.c_int32), ('finalize', ctypes.c_int32),
+                ('rs_ynext', ctypes.c_int32)]
+
+
+# the arrays a handle of sporco_amd_cmod_pgm_create adds, its phases and out[] slots (SPORCO_AMD_PGMC_*)
+CMOD_XPRV, CMOD_YALT, CMOD_PG, CMOD_PZ, CMOD_ZZ = range(6, 11)
+PGMC_PHASE_YROBUST, PGMC_PHASE_GRAD, PGMC_PHASE_GZ2, PGMC_PHASE_PROX, PGMC_PHASE_DFID = 1, 2, 4, 8, 16
+PGMC_FY, PGMC_FX, PGMC_DXG, PGMC_DXY2, PGMC_CNSTR = range(5)
+PGMC_RS2, PGMC_G2, PGMC_GZ2, PGMC_BBXG, PGMC_BBG2 = range(6, 11)
 
 
 class RpcaParams(ctypes.Structure):
@@ -532,6 +551,9 @@ def load(path=None):
         'sporco_amd_cmod_download': [vp, ctypes.c_int, vp],
         'sporco_amd_cmod_iter': [vp, ctypes.POINTER(CmodParams), dptr],
         'sporco_amd_cmod_dfid': [vp, ctypes.c_int, dptr],
+        'sporco_amd_cmod_pgm_create': [ctypes.c_int, i32, i32, i64, ctypes.c_int, vp, ctypes.POINTER(vp)],
+        'sporco_amd_cmod_pgm_set_weight': [vp, vp, ctypes.c_int],
+        'sporco_amd_cmod_pgm_step': [vp, ctypes.POINTER(CmodPgmParams), dptr],
         'sporco_amd_cmod_profile': [vp, ctypes.c_int],
         'sporco_amd_cmod_profile_read': [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), dptr,
                                          ctypes.POINTER(i64)],
@@ -1703,11 +1725,13 @@ class CmodHandle(object):
     copied or :class:`sporco_amd.device.DeviceArray` that are read in place (the handle keeps them alive);
     X / Y / U (N, M), host arrays in and out."""
 
+    _create = 'sporco_amd_cmod_create'
+
     def __init__(self, N, M, K, dtype, device=0, stream=None):
         self.dims = (int(N), int(M), int(K))
         self.dtype = np.dtype(dtype)
         h = ctypes.c_void_p()
-        check(lib().sporco_amd_cmod_create(dtype_code(dtype), int(N), int(M), int(K), int(device),
+        check(getattr(lib(), self._create)(dtype_code(dtype), int(N), int(M), int(K), int(device),
                                            ctypes.c_void_p(stream or 0), ctypes.byref(h)))
         self._h = h
         self._lib = lib()
@@ -1807,6 +1831,47 @@ class CmodHandle(object):
             if cnt.value:
                 res[name.value.decode()] = (ms.value, cnt.value)
         return res
+
+
+class PgmCmodHandle(CmodHandle):
+    """Owner of one device-side pgm.cmod CnstrMOD / WeightedCnstrMOD problem (sporco_amd_cmod_pgm_*): a
+    :class:`CmodHandle` without Gram and solve matrices, with the arrays of the proximal gradient iteration
+    (``CMOD_XPRV`` ... ``CMOD_ZZ``) and the weight W (N, K), a host array that is copied or a
+    :class:`sporco_amd.device.DeviceArray` that is read in place."""
+
+    _create = 'sporco_amd_cmod_pgm_create'
+
+    def plan(self):
+        """``dict(KS, slab, slabs, row_blocks, tiles_per_wave, mfma, lds_grad, lds_prox)``: the columns of K staged
+        per step, the columns of a slab, the slabs, the blocks of 32 rows of cmod_pgm_grad, the 16-column tiles of G
+        a wave accumulates, whether the products use the matrix instruction, the bytes of LDS of a workgroup of
+        cmod_pgm_grad and cmod_pgm_prox."""
+        out = (ctypes.c_int64 * 8)()
+        check(self._lib.sporco_amd_cmod_plan(self._h, out))
+        return dict(zip(('KS', 'slab', 'slabs', 'row_blocks', 'tiles_per_wave', 'mfma', 'lds_grad', 'lds_prox'),
+                        (int(v) for v in out)))
+
+    def set_weight(self, W):
+        """W (N, K), or None: the scalar weight of the step's parameters."""
+        if W is None:
+            check(self._lib.sporco_amd_cmod_pgm_set_weight(self._h, None, 0))
+            self._keep.pop('W', None)
+            return
+        self._set_big(self._lib.sporco_amd_cmod_pgm_set_weight, 'W', W, self.dims[0])
+
+    def step(self, params, read=True):
+        """The phases ``params`` asks for and, with ``params.finalize``, the reduction; the ``PGMC_*`` sums, or None
+        without ``read``."""
+        if not read:
+            check(self._lib.sporco_amd_cmod_pgm_step(self._h, ctypes.byref(params), None))
+            return None
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(self._lib.sporco_amd_cmod_pgm_step(self._h, ctypes.byref(params), out))
+        return list(out)
+
+    def dfid(self):
+        """``sum W (X Z - S)^2`` of the iterate."""
+        return CmodHandle.dfid(self, CMOD_X)
 
 
 class RpcaHandle(object):

@@ -131,7 +131,7 @@ template <typename T> struct Cmod : CmodBase {
         have_q = true;
     }
 
-    T *kbuf(int var) {
+    virtual T *kbuf(int var) {
         switch (var) {
         case SPORCO_AMD_CMOD_X: return xk;
         case SPORCO_AMD_CMOD_Y: return yk;

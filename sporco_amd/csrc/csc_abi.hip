@@ -1487,6 +1487,40 @@ int sporco_amd_cmod_dfid(sporco_amd_cmod_t h, int var, double out[SPORCO_AMD_OUT
     SA_API_END
 }
 
+// ---- pgm.cmod CnstrMOD / WeightedCnstrMOD: a cmod handle with the arrays of the proximal gradient iteration ---------
+int sporco_amd_cmod_pgm_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_cmod_t *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out != nullptr, "null argument");
+    SA_REQUIRE(N >= 1 && M >= 1 && K >= 1, "cmod: N >= 1, M >= 1, K >= 1");
+    SA_REQUIRE(N <= SPORCO_AMD_CMOD_MAX_DIM && M <= SPORCO_AMD_CMOD_MAX_DIM,
+               "cmod: the kernels serve dictionaries of up to 512 rows and 512 columns");
+    SA_REQUIRE(K < ((int64_t)1 << 31), "cmod: fewer than 2^31 signals");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    std::unique_ptr<sporco_amd_cmod> h(new sporco_amd_cmod);
+    h->device = device;
+    h->impl.reset(make_pgm_cmod(dtype, N, M, K, device, stream));
+    *out = h.release();
+    SA_API_END
+}
+
+int sporco_amd_cmod_pgm_set_weight(sporco_amd_cmod_t h, const void *W, int on_device) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    h->impl->set_weight(W, on_device != 0);
+    SA_API_END
+}
+
+int sporco_amd_cmod_pgm_step(sporco_amd_cmod_t h, const sporco_amd_cmod_pgm_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
+    SA_API_BEGIN
+    SA_CMOD_HANDLE(h);
+    SA_REQUIRE(p != nullptr, "null argument");
+    h->impl->pgm_step(*p, out);
+    SA_API_END
+}
+
 int sporco_amd_cmod_profile(sporco_amd_cmod_t h, int enable) {
     SA_API_BEGIN
     SA_CMOD_HANDLE(h);

@@ -44,7 +44,9 @@ const char *kProfNames[PS_COUNT] = {"fft_r2c_rows",     "fft_c2c_cols_fwd", "sm_
                                     "bpdn_joint_apply", "bpdn_lsc",
                                     "bpdn_pgm_step",    "bpdn_pgm_ystep",
                                     "cmod_gram",        "cmod_gram_reduce", "cmod_rhs",
-                                    "cmod_iter",        "cmod_dfid",        "rpca_gram",
+                                    "cmod_iter",        "cmod_dfid",        "cmod_pgm_grad",
+                                    "cmod_pgm_reduce",  "cmod_pgm_prox",    "cmod_pgm_dfid",
+                                    "cmod_pgm_yrobust", "rpca_gram",
                                     "rpca_gram_reduce", "rpca_iter"};
 
 // Environment switches (include/sporco_amd.h lists them; tests and measurements, none is needed in
@@ -665,6 +667,7 @@ template <typename T> struct Csc : CscBase {
 #include "api_bpdn.inc"
 #include "api_pgm_bpdn.inc"
 #include "api_cmod.inc"
+#include "api_pgm_cmod.inc"
 #include "api_rpca.inc"
 
 CscBase *make_csc(const sporco_amd_dims &dims, int dict_channels, int device, void *stream, int depth) {

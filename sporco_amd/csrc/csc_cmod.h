@@ -21,7 +21,8 @@
 //     cmod_iter  a workgroup owns 16 columns of the dictionary and all N rows: X = B Q[:, block] by bpdn_product
 //                (the tile is Q's column block, the left operand B), relax, Y' = Pcn(AX + U) with the column mean and
 //                norm reduced inside the workgroup in a fixed order, U' = U + AX - Y', and the sums of cmod_sums.
-//     cmod_dfid  sum (F Z - S)^2 over column blocks of K: the left operand is X or Y as stored, the tile a block of Z.
+//     cmod_dfid  sum w (F Z - S)^2 over column blocks of K: the left operand is X or Y as stored, the tile a block of Z;
+//                the weight w (pgm.cmod, csc_pgm_cmod.h) is 1 unless it is given, and a product by 1 is exact.
 // bpdn_product fits both products; B has to lie in global memory for it, which is why cmod_rhs is a launch of its own.
 #pragma once
 
@@ -41,6 +42,16 @@ struct CmodPlan {
     int M16, N16, M4, RB, CB, nsplit;
     int64_t slab;
 };
+// the slab rule: `blocks` workgroups share a slab of K; about two workgroups a compute unit of a 256-unit device, at
+// least one step a slab.  Returns the columns of a slab, a multiple of kCmodKS; *nsplit: the slabs.
+inline int64_t cmod_slab(int64_t K, int blocks, int *nsplit) {
+    int want = (512 + blocks - 1) / blocks;
+    if (want > kCmodMaxSplits) want = kCmodMaxSplits;
+    int64_t slab = (K + want - 1) / want;
+    slab = (slab + kCmodKS - 1) / kCmodKS * kCmodKS;
+    *nsplit = (int)((K + slab - 1) / slab);
+    return slab;
+}
 inline CmodPlan cmod_plan(int N, int M, int64_t K) {
     CmodPlan p;
     p.M16 = bpdn_up(M, 16);
@@ -48,13 +59,7 @@ inline CmodPlan cmod_plan(int N, int M, int64_t K) {
     p.M4 = bpdn_up(M, 4);
     p.RB = (p.M16 + p.N16 + kCmodBlk - 1) / kCmodBlk;
     p.CB = (p.M16 + kCmodBlk - 1) / kCmodBlk;
-    // about two workgroups a compute unit of a 256-unit device, at least one step a slab
-    int want = (512 + p.RB * p.CB - 1) / (p.RB * p.CB);
-    if (want > kCmodMaxSplits) want = kCmodMaxSplits;
-    int64_t slab = (K + want - 1) / want;
-    slab = (slab + kCmodKS - 1) / kCmodKS * kCmodKS;
-    p.slab = slab;
-    p.nsplit = (int)((K + slab - 1) / slab);
+    p.slab = cmod_slab(K, p.RB * p.CB, &p.nsplit);
     return p;
 }
 template <typename T> inline size_t cmod_gram_lds_bytes() { return sizeof(T) * 2 * kCmodBlk * kCmodLd; }
@@ -89,10 +94,13 @@ template <typename T> struct CmodArgs {
 
 template <typename T> struct CmodDfidArgs {
     const T *fk = nullptr;       // [M4][N16]  the dictionary variable
-    const T *z = nullptr, *s = nullptr;
+    const T *z = nullptr, *s = nullptr;       // s == nullptr: S = 0, the sum is || F Z ||^2
+    const T *w = nullptr;        // (N, K) weight that multiplies (F Z - S)^2, or nullptr: w_s
+    T w_s = T(1);
     int M = 1, N = 1, KB = 16, form = BPDN_FORM_PLAIN;
     int64_t K = 1;
-    double *partials = nullptr;  // one double per workgroup
+    double *partials = nullptr;  // one double per workgroup, `stride` doubles apart
+    int stride = 1;
 };
 
 // part <- the slab partials of [Z; S] Z^T.  Returns the workgroups.

@@ -4,6 +4,7 @@
 #include "csc_cmod.h"
 #include "csc_bpdn_product.h"
 #include "csc_kernels_dev.h"
+#include "csc_cmod_cols.h"
 
 namespace sporco_amd {
 
@@ -130,37 +131,6 @@ template <typename T> __global__ void __launch_bounds__(kThreads) cmod_rhs_kerne
     }
 }
 
-// the sum of `v` over the 16 threads of a column (threads t with the same t & 15), in the order of t >> 4
-__device__ __forceinline__ double cm_col_sum(double v, double *cs) {
-    cs[threadIdx.x] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += cs[q * 16 + ((int)threadIdx.x & 15)];
-    __syncthreads();
-    return s;
-}
-
-// mean (zero_mean) and norm of the thread's column of the tile `t` ([N][16]), as Pcn wants them
-// (cmod.py:286-342): mean = sum / N, norm = sqrt(sum (v - mean)^2) with 0 replaced by 1
-template <typename T>
-__device__ __forceinline__ void cm_col_stats(const T *t, int N, int zero_mean, double *cs, T &mean, T &nrm) {
-    const int c = (int)threadIdx.x & 15;
-    mean = T(0);
-    if (zero_mean) {
-        double s = 0.0;
-        for (int n = (int)threadIdx.x >> 4; n < N; n += 16) s += (double)t[n * 16 + c];
-        mean = (T)(cm_col_sum(s, cs) / (double)N);
-    }
-    double ss = 0.0;
-    for (int n = (int)threadIdx.x >> 4; n < N; n += 16) {
-        const double d = (double)(t[n * 16 + c] - mean);
-        ss += d * d;
-    }
-    nrm = (T)sqrt(cm_col_sum(ss, cs));
-    if (nrm == T(0)) nrm = T(1);
-}
-
 // one workgroup per 16 columns of the dictionary
 template <typename T, int FORM> __global__ void __launch_bounds__(kThreads) cmod_iter_kernel(const CmodArgs<T> a) {
     const int M = a.M, N = a.N;
@@ -253,13 +223,14 @@ template <typename T, int KB, int FORM> __global__ void __launch_bounds__(kThrea
         bpdn_product<T, KB / 16, FORM>(a.fk, N16, M4, tz, LDB, [&](int i, int j, T v) {
             const int64_t col = c0 + j;
             if (i < N && col < a.K) {
-                const double d = (double)(v - a.s[(int64_t)i * a.K + col]);
-                acc[0] += d * d;
+                const int64_t off = (int64_t)i * a.K + col;
+                const double d = (double)(a.s ? v - a.s[off] : v);
+                acc[0] += (double)(a.w ? a.w[off] : a.w_s) * (d * d);
             }
         });
         __syncthreads();
     }
-    block_sum_store<1>(acc, scratch, a.partials + blockIdx.x);
+    block_sum_store<1>(acc, scratch, a.partials + (int64_t)blockIdx.x * a.stride);
 }
 
 template <auto KERNEL, typename A> void cm_launch(dim3 grid, size_t lds, hipStream_t st, const A &a) {
@@ -339,7 +310,7 @@ template <typename T> int launch_cmod_iter(hipStream_t st, const CmodArgs<T> &a)
 template <typename T> int launch_cmod_dfid(hipStream_t st, const CmodDfidArgs<T> &a) {
     SA_REQUIRE(cm_dims_ok(a.M, a.N) && a.K >= 1 && a.K < (int64_t)1 << 31 && a.KB == bpdn_kb<T>(a.M, a.N),
                "cmod_dfid: bad argument");
-    SA_REQUIRE(a.fk && a.z && a.s && a.partials, "cmod_dfid: null argument");
+    SA_REQUIRE(a.fk && a.z && a.partials && a.stride >= 1, "cmod_dfid: null argument");
     cm_check_form<T>(a.form, "cmod_dfid: bad form");
     const size_t lds = bpdn_lds_bytes<T>(a.M, a.N);
     SA_REQUIRE(lds <= (size_t)160 * 1024, "cmod_dfid: the tile does not fit in LDS");

@@ -32,6 +32,7 @@
 #include "csc_bpdn.h"
 #include "csc_pgm_bpdn.h"
 #include "csc_cmod.h"
+#include "csc_pgm_cmod.h"
 #include "csc_rpca.h"
 #include "fft.h"
 
@@ -144,6 +145,11 @@ enum ProfSlot {
     PS_CMOD_RHS,                // ... the right-hand side of the x step
     PS_CMOD_ITER,               // ... the whole iteration of a block of 16 dictionary columns
     PS_CMOD_DFID,               // ... sum (F Z - S)^2
+    PS_CMOD_PGM_GRAD,           // pgm.cmod CnstrMOD / WeightedCnstrMOD: the slab partials of (w (Y Z - S)) Z^T (csc_pgm_cmod.h)
+    PS_CMOD_PGM_REDUCE,         // ... added in slab order, || G ||^2 and the Barzilai-Borwein sums
+    PS_CMOD_PGM_PROX,           // ... X' = Pcn(Y - G / L), the next Y, the sums of a block of 16 dictionary columns
+    PS_CMOD_PGM_DFID,           // ... sum w (X' Z - S)^2, || G Z ||^2 (cmod_dfid with the weight)
+    PS_CMOD_PGM_YROBUST,        // ... the Y of the robust backtracking rule
     PS_RPCA_GRAM,               // RobustPCA / prox_nuclear: the slab partials of the Gram matrix of V (csc_rpca.h)
     PS_RPCA_GRAM_REDUCE,        // ... added in slab order
     PS_RPCA_ITER,               // ... X = V T, relax, y step, u step, sums (apply: X alone)
@@ -429,9 +435,16 @@ struct CmodBase {
     virtual void download(int var, void *dst) = 0;
     virtual void iter(const sporco_amd_cmod_params &p, double *out_host) = 0;
     virtual void dfid(int var, double *out_host) = 0;
+    // the proximal gradient steps of pgm.cmod (api_pgm_cmod.inc): served by a handle of sporco_amd_cmod_pgm_create
+    virtual void set_weight(const void *, bool) { no_pgm(); }
+    virtual void pgm_step(const sporco_amd_cmod_pgm_params &, double *) { no_pgm(); }
+    [[noreturn]] static void no_pgm() {
+        throw Error(SPORCO_AMD_EINVAL, "cmod: the handle was not made by sporco_amd_cmod_pgm_create");
+    }
     Profiler prof;
 };
 CmodBase *make_cmod(int dtype, int N, int M, int64_t K, int device, void *stream);
+CmodBase *make_pgm_cmod(int dtype, int N, int M, int64_t K, int device, void *stream);
 
 // The handle of RobustPCA and of the stateless prox_nuclear / norm_nuclear (api_rpca.inc): X, Y, U of one (R, C)
 // problem as NumPy has them, its own or a borrowed S, the Gram matrix and its slab partials, T, and a stream.

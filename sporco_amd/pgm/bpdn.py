@@ -195,6 +195,11 @@ class BPDN(pgm.PGM):
     def getmin(self):
         return self.X
 
+    def getcoef_device(self):
+        """The current ``X`` as a :class:`sporco_amd.device.DeviceArray` over the handle's own buffer: no copy.  The
+        two X arrays change roles with every step, so the view is taken again after each ``solve``."""
+        return self._dev.device_view(_lib.BPDN_X)
+
     def finish_solve(self):
         self._dev.sync()
 
