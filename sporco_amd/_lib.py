@@ -645,8 +645,92 @@ def _carr(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-class Solver(object):
+class _Handle(object):
+    """What the owners of an opaque C handle share.  ``_prefix`` names the family's entry points
+    (``<_prefix>_destroy``, ``_sync``, ``_profile``, ``_profile_read``, ...)."""
+
+    _prefix = None
+    _all_slots = False      # profile_read returns every slot, not only those that ran
+
+    def _open(self, create, *args):
+        """``create(*args, &handle)``: the family's arguments, the device and the stream."""
+        h = ctypes.c_void_p()
+        check(create(*args, ctypes.byref(h)))
+        self._h = h
+        self._lib = lib()
+
+    def _fn(self, name):
+        return getattr(self._lib, self._prefix + '_' + name)
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._fn('destroy')(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        check(self._fn('sync')(self._h))
+
+    def _sums(self, fn, *args):
+        """``fn(handle, *args, out)``: the ``OUT_COUNT`` sums of a call as a list."""
+        out = (ctypes.c_double * OUT_COUNT)()
+        check(fn(self._h, *args, out))
+        return list(out)
+
+    def profile(self, enable):
+        check(self._fn('profile')(self._h, 1 if enable else 0))
+
+    def profile_read(self):
+        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran (a
+        :class:`Solver`: for every slot), and reset the counters."""
+        res = {}
+        read = self._fn('profile_read')
+        for slot in range(self._lib.sporco_amd_profile_slots()):
+            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
+            check(read(self._h, slot, ctypes.byref(name), ctypes.byref(ms), ctypes.byref(cnt)))
+            if cnt.value or self._all_slots:
+                res[name.value.decode()] = (ms.value, cnt.value)
+        return res
+
+
+class _PlaneArrays(object):
+    """``upload`` / ``download`` of the handles whose variables are (H, W, P) arrays, host or device side; the class
+    has ``var_shape(var)``."""
+
+    def upload(self, var, a):
+        """``a``: a host array, a device pointer (int) of an array of the variable's size, or None
+        (a weight goes back to its scalar)."""
+        up = self._fn('upload')
+        if a is None:
+            check(up(self._h, int(var), None, 0))
+        elif isinstance(a, int):
+            check(up(self._h, int(var), ctypes.c_void_p(a), 1))
+        else:
+            a = _carr(a, self.dtype)
+            if a.size != int(np.prod(self.var_shape(var))):
+                raise ValueError("array of %d elements for a variable of shape %s" % (a.size, self.var_shape(var)))
+            check(up(self._h, int(var), _ptr(a), 0))
+
+    def download(self, var, dst_ptr=None):
+        """To a new host array, or (``dst_ptr``: device pointer) device to device."""
+        if dst_ptr is not None:
+            check(self._fn('download')(self._h, int(var), ctypes.c_void_p(dst_ptr), 1))
+            return None
+        out = np.empty(self.var_shape(var), dtype=self.dtype)
+        check(self._fn('download')(self._h, int(var), _ptr(out), 0))
+        return out
+
+
+class Solver(_Handle):
     """Owner of one device-side ConvBPDN problem (opaque C handle)."""
+
+    _prefix = 'sporco_amd_csc'
+    _all_slots = True       # (the callers of profile_read filter)
 
     def __init__(self, H, W, C, N, K, dtype, device=0, stream=None, Cd=1, depth=1):
         """``C``: channels of the signal.  ``Cd`` > 1 (== C): multi-channel dictionary, the
@@ -661,28 +745,12 @@ class Solver(object):
         self.cdtype = np.dtype(np.complex64 if self.dtype == np.float32
                                else np.complex128)
         d = Dims(int(H), int(W), int(C), int(N), int(K), dtype_code(dtype))
-        h = ctypes.c_void_p()
         if self.depth > 1:
-            check(lib().sporco_amd_csc_create_volume(ctypes.byref(d), self.depth, int(device),
-                                                     ctypes.c_void_p(stream or 0), ctypes.byref(h)))
+            self._open(lib().sporco_amd_csc_create_volume, ctypes.byref(d), self.depth, int(device),
+                       ctypes.c_void_p(stream or 0))
         else:
-            check(lib().sporco_amd_csc_create_mc(ctypes.byref(d), self.Cd, int(device),
-                                                 ctypes.c_void_p(stream or 0),
-                                                 ctypes.byref(h)))
-        self._h = h
-        self._lib = lib()
-
-    # -- lifetime ---------------------------------------------------------
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sporco_amd_csc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._open(lib().sporco_amd_csc_create_mc, ctypes.byref(d), self.Cd, int(device),
+                       ctypes.c_void_p(stream or 0))
 
     # -- shapes -----------------------------------------------------------
     @property
@@ -720,9 +788,6 @@ class Solver(object):
         return (H, W, C, N, K), self.dtype
 
     # -- set-up -----------------------------------------------------------
-    def sync(self):
-        check(self._lib.sporco_amd_csc_sync(self._h))
-
     def stream_handle(self):
         """hipStream_t (as an int) of every launch this handle makes."""
         out = ctypes.c_void_p(0)
@@ -1301,53 +1366,21 @@ class Solver(object):
     def ifft_var(self, cplx_var, real_var):
         check(self._lib.sporco_amd_csc_ifft_var(self._h, cplx_var, real_var))
 
-    # -- timing -------------------------------------------------------------
-    def profile(self, enable):
-        check(self._lib.sporco_amd_csc_profile(self._h, 1 if enable else 0))
 
-    def profile_read(self):
-        """Return {kernel name: (total_ms, launches)} and reset the counters."""
-        res = {}
-        for slot in range(self._lib.sporco_amd_profile_slots()):
-            name = ctypes.c_char_p()
-            ms = ctypes.c_double(0.0)
-            cnt = ctypes.c_int64(0)
-            check(self._lib.sporco_amd_csc_profile_read(self._h, slot, ctypes.byref(name),
-                                                        ctypes.byref(ms), ctypes.byref(cnt)))
-            res[name.value.decode()] = (ms.value, cnt.value)
-        return res
-
-
-class TvdHandle(object):
+class TvdHandle(_PlaneArrays, _Handle):
     """Owner of one device-side TVL2Denoise problem (sporco_amd_tvd_*): arrays of shape
     (H, W, P); ``vector_tv``: the l2 norm of the y step also runs over the first of the trailing axes
     (``C`` channels).  ``l1``: a TVL1Denoise problem (sporco_amd_tvl1_create) -- Y and U have three
     blocks, the last the data block."""
 
+    _prefix = 'sporco_amd_tvd'
+
     def __init__(self, H, W, P, dtype, C=1, vector_tv=False, device=0, stream=None, l1=False):
         self.dims = (int(H), int(W), int(P))
         self.dtype = np.dtype(dtype)
         self.blocks = 3 if l1 else 2
-        h = ctypes.c_void_p()
-        create = lib().sporco_amd_tvl1_create if l1 else lib().sporco_amd_tvd_create
-        check(create(dtype_code(dtype), int(H), int(W), int(P), int(C), 1 if vector_tv else 0, int(device),
-                     ctypes.c_void_p(stream or 0), ctypes.byref(h)))
-        self._h = h
-        self._lib = lib()
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sporco_amd_tvd_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sync(self):
-        check(self._lib.sporco_amd_tvd_sync(self._h))
+        self._open(lib().sporco_amd_tvl1_create if l1 else lib().sporco_amd_tvd_create, dtype_code(dtype), int(H),
+                   int(W), int(P), int(C), 1 if vector_tv else 0, int(device), ctypes.c_void_p(stream or 0))
 
     def plan(self):
         """``dict(V, items, strips, R, nseg, TW)``: elements per item, items per row, strips per row,
@@ -1359,90 +1392,33 @@ class TvdHandle(object):
     def var_shape(self, var):
         return ((self.blocks,) if var in (TVD_Y, TVD_U) else ()) + self.dims
 
-    def upload(self, var, a):
-        """``a``: a host array, a device pointer (int) of an array of the variable's size, or None
-        (a weight goes back to its scalar)."""
-        if a is None:
-            check(self._lib.sporco_amd_tvd_upload(self._h, int(var), None, 0))
-        elif isinstance(a, int):
-            check(self._lib.sporco_amd_tvd_upload(self._h, int(var), ctypes.c_void_p(a), 1))
-        else:
-            a = _carr(a, self.dtype)
-            if a.size != int(np.prod(self.var_shape(var))):
-                raise ValueError("array of %d elements for a variable of shape %s" % (a.size, self.var_shape(var)))
-            check(self._lib.sporco_amd_tvd_upload(self._h, int(var), _ptr(a), 0))
-
-    def download(self, var, dst_ptr=None):
-        """To a new host array, or (``dst_ptr``: device pointer) device to device."""
-        if dst_ptr is not None:
-            check(self._lib.sporco_amd_tvd_download(self._h, int(var), ctypes.c_void_p(dst_ptr), 1))
-            return None
-        out = np.empty(self.var_shape(var), dtype=self.dtype)
-        check(self._lib.sporco_amd_tvd_download(self._h, int(var), _ptr(out), 0))
-        return out
-
     def sweeps(self, params, n):
         check(self._lib.sporco_amd_tvd_sweeps(self._h, ctypes.byref(params), int(n)))
 
-    def _sums(self, fn, params):
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(fn(self._h, ctypes.byref(params), out))
-        return list(out)
-
     def gsres(self, params):
-        return self._sums(self._lib.sporco_amd_tvd_gsres, params)
+        return self._sums(self._lib.sporco_amd_tvd_gsres, ctypes.byref(params))
 
     def ystep(self, params):
-        return self._sums(self._lib.sporco_amd_tvd_ystep, params)
+        return self._sums(self._lib.sporco_amd_tvd_ystep, ctypes.byref(params))
 
     def adjoint(self):
         check(self._lib.sporco_amd_tvd_adjoint(self._h))
 
-    def profile(self, enable):
-        check(self._lib.sporco_amd_tvd_profile(self._h, 1 if enable else 0))
 
-    def profile_read(self):
-        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
-        res = {}
-        for slot in range(self._lib.sporco_amd_profile_slots()):
-            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
-            check(self._lib.sporco_amd_tvd_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
-                                                        ctypes.byref(cnt)))
-            if cnt.value:
-                res[name.value.decode()] = (ms.value, cnt.value)
-        return res
-
-
-class TvdcHandle(object):
+class TvdcHandle(_PlaneArrays, _Handle):
     """Owner of one device-side TVL2Deconv problem (sporco_amd_tvdc_*), or with ``l1`` of a TVL1Deconv
     problem (sporco_amd_tvl1dc_create: Y and U have three blocks, the last the data block).  Arrays of
     shape (H, W, P); ``PA``: the planes of the kernel A, ``P`` or 1."""
+
+    _prefix = 'sporco_amd_tvdc'
 
     def __init__(self, H, W, P, dtype, C=1, vector_tv=False, PA=1, device=0, stream=None, l1=False):
         self.dims = (int(H), int(W), int(P))
         self.PA = int(PA)
         self.dtype = np.dtype(dtype)
         self.blocks = 3 if l1 else 2
-        h = ctypes.c_void_p()
-        create = lib().sporco_amd_tvl1dc_create if l1 else lib().sporco_amd_tvdc_create
-        check(create(dtype_code(dtype), int(H), int(W), int(P), int(C), 1 if vector_tv else 0, int(PA), int(device),
-                     ctypes.c_void_p(stream or 0), ctypes.byref(h)))
-        self._h = h
-        self._lib = lib()
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sporco_amd_tvdc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sync(self):
-        check(self._lib.sporco_amd_tvdc_sync(self._h))
+        self._open(lib().sporco_amd_tvl1dc_create if l1 else lib().sporco_amd_tvdc_create, dtype_code(dtype), int(H),
+                   int(W), int(P), int(C), 1 if vector_tv else 0, int(PA), int(device), ctypes.c_void_p(stream or 0))
 
     def plan(self):
         """``dict(V, items, strips, R, nseg, TW, SV, sblocks)``: elements per item, items per row, strips per
@@ -1454,28 +1430,6 @@ class TvdcHandle(object):
 
     def var_shape(self, var):
         return ((self.blocks,) if var in (TVDC_Y, TVDC_U) else ()) + self.dims
-
-    def upload(self, var, a):
-        """``a``: a host array, a device pointer (int) of an array of the variable's size, or None
-        (a weight goes back to its scalar)."""
-        if a is None:
-            check(self._lib.sporco_amd_tvdc_upload(self._h, int(var), None, 0))
-        elif isinstance(a, int):
-            check(self._lib.sporco_amd_tvdc_upload(self._h, int(var), ctypes.c_void_p(a), 1))
-        else:
-            a = _carr(a, self.dtype)
-            if a.size != int(np.prod(self.var_shape(var))):
-                raise ValueError("array of %d elements for a variable of shape %s" % (a.size, self.var_shape(var)))
-            check(self._lib.sporco_amd_tvdc_upload(self._h, int(var), _ptr(a), 0))
-
-    def download(self, var, dst_ptr=None):
-        """To a new host array, or (``dst_ptr``: device pointer) device to device."""
-        if dst_ptr is not None:
-            check(self._lib.sporco_amd_tvdc_download(self._h, int(var), ctypes.c_void_p(dst_ptr), 1))
-            return None
-        out = np.empty(self.var_shape(var), dtype=self.dtype)
-        check(self._lib.sporco_amd_tvdc_download(self._h, int(var), _ptr(out), 0))
-        return out
 
     def set_kernel(self, a, ah=None, aw=None):
         """``a``: a host array of shape (ah, aw, PA), or a device pointer (int) with ``ah``, ``aw`` given."""
@@ -1491,54 +1445,23 @@ class TvdcHandle(object):
         check(self._lib.sporco_amd_tvdc_xstep(self._h, ctypes.byref(params)))
 
     def ystep(self, params):
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_tvdc_ystep(self._h, ctypes.byref(params), out))
-        return list(out)
+        return self._sums(self._lib.sporco_amd_tvdc_ystep, ctypes.byref(params))
 
     def adjoint(self):
         check(self._lib.sporco_amd_tvdc_adjoint(self._h))
 
-    def profile(self, enable):
-        check(self._lib.sporco_amd_tvdc_profile(self._h, 1 if enable else 0))
 
-    def profile_read(self):
-        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
-        res = {}
-        for slot in range(self._lib.sporco_amd_profile_slots()):
-            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
-            check(self._lib.sporco_amd_tvdc_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
-                                                         ctypes.byref(cnt)))
-            if cnt.value:
-                res[name.value.decode()] = (ms.value, cnt.value)
-        return res
-
-
-class SplHandle(object):
+class SplHandle(_PlaneArrays, _Handle):
     """Owner of one device-side SplineL1 problem (sporco_amd_spl_*).  Arrays of shape (H, W, P); a 1-D
     signal of N samples is H = 1, W = N."""
+
+    _prefix = 'sporco_amd_spl'
 
     def __init__(self, H, W, P, dtype, device=0, stream=None):
         self.dims = (int(H), int(W), int(P))
         self.dtype = np.dtype(dtype)
-        h = ctypes.c_void_p()
-        check(lib().sporco_amd_spl_create(dtype_code(dtype), int(H), int(W), int(P), int(device),
-                                          ctypes.c_void_p(stream or 0), ctypes.byref(h)))
-        self._h = h
-        self._lib = lib()
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sporco_amd_spl_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sync(self):
-        check(self._lib.sporco_amd_spl_sync(self._h))
+        self._open(lib().sporco_amd_spl_create, dtype_code(dtype), int(H), int(W), int(P), int(device),
+                   ctypes.c_void_p(stream or 0))
 
     def plan(self):
         """``dict(V, pairs, sblocks, yblocks)``: planes per access, the row pairs {k1, H - k1} of ``spl_solve``,
@@ -1547,79 +1470,28 @@ class SplHandle(object):
         check(self._lib.sporco_amd_spl_plan(self._h, out))
         return dict(zip(('V', 'pairs', 'sblocks', 'yblocks'), (int(v) for v in out)))
 
-    def upload(self, var, a):
-        """``a``: a host array, a device pointer (int) of an array of the variable's size, or None
-        (the weight goes back to its scalar)."""
-        if a is None:
-            check(self._lib.sporco_amd_spl_upload(self._h, int(var), None, 0))
-        elif isinstance(a, int):
-            check(self._lib.sporco_amd_spl_upload(self._h, int(var), ctypes.c_void_p(a), 1))
-        else:
-            a = _carr(a, self.dtype)
-            if a.size != int(np.prod(self.dims)):
-                raise ValueError("array of %d elements for a variable of shape %s" % (a.size, self.dims))
-            check(self._lib.sporco_amd_spl_upload(self._h, int(var), _ptr(a), 0))
-
-    def download(self, var, dst_ptr=None):
-        """To a new host array, or (``dst_ptr``: device pointer) device to device."""
-        if dst_ptr is not None:
-            check(self._lib.sporco_amd_spl_download(self._h, int(var), ctypes.c_void_p(dst_ptr), 1))
-            return None
-        out = np.empty(self.dims, dtype=self.dtype)
-        check(self._lib.sporco_amd_spl_download(self._h, int(var), _ptr(out), 0))
-        return out
+    def var_shape(self, var):
+        return self.dims
 
     def xstep(self, params):
         check(self._lib.sporco_amd_spl_xstep(self._h, ctypes.byref(params)))
 
     def ystep(self, params):
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_spl_ystep(self._h, ctypes.byref(params), out))
-        return list(out)
-
-    def profile(self, enable):
-        check(self._lib.sporco_amd_spl_profile(self._h, 1 if enable else 0))
-
-    def profile_read(self):
-        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
-        res = {}
-        for slot in range(self._lib.sporco_amd_profile_slots()):
-            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
-            check(self._lib.sporco_amd_spl_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
-                                                        ctypes.byref(cnt)))
-            if cnt.value:
-                res[name.value.decode()] = (ms.value, cnt.value)
-        return res
+        return self._sums(self._lib.sporco_amd_spl_ystep, ctypes.byref(params))
 
 
-class BpdnHandle(object):
+class BpdnHandle(_Handle):
     """Owner of one device-side BPDN / BPDNJoint / ElasticNet problem (sporco_amd_bpdn_*): D (N, M), S (N, K),
     X / Y / U (M, K), host arrays in and out."""
 
+    _prefix = 'sporco_amd_bpdn'
     _create = 'sporco_amd_bpdn_create'
 
     def __init__(self, N, M, K, dtype, device=0, stream=None):
         self.dims = (int(N), int(M), int(K))
         self.dtype = np.dtype(dtype)
-        h = ctypes.c_void_p()
-        check(getattr(lib(), self._create)(dtype_code(dtype), int(N), int(M), int(K), int(device),
-                                           ctypes.c_void_p(stream or 0), ctypes.byref(h)))
-        self._h = h
-        self._lib = lib()
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sporco_amd_bpdn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sync(self):
-        check(self._lib.sporco_amd_bpdn_sync(self._h))
+        self._open(getattr(lib(), self._create), dtype_code(dtype), int(N), int(M), int(K), int(device),
+                   ctypes.c_void_p(stream or 0))
 
     def plan(self):
         """``dict(KB, blocks, mfma, lds)``: the columns of a workgroup's block, the workgroups, whether the
@@ -1664,9 +1536,7 @@ class BpdnHandle(object):
         return out
 
     def iter(self, params):
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_bpdn_iter(self._h, ctypes.byref(params), out))
-        return list(out)
+        return self._sums(self._lib.sporco_amd_bpdn_iter, ctypes.byref(params))
 
     def device_view(self, var):
         """A :class:`sporco_amd.device.DeviceArray` over the buffer of variable ``var``: no copy, and the view
@@ -1678,20 +1548,6 @@ class BpdnHandle(object):
             raise ValueError("the variable has no device array")
         return DeviceArray(self._shape(var), self.dtype, ptr=p.value, base=self)
 
-    def profile(self, enable):
-        check(self._lib.sporco_amd_bpdn_profile(self._h, 1 if enable else 0))
-
-    def profile_read(self):
-        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
-        res = {}
-        for slot in range(self._lib.sporco_amd_profile_slots()):
-            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
-            check(self._lib.sporco_amd_bpdn_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
-                                                         ctypes.byref(cnt)))
-            if cnt.value:
-                res[name.value.decode()] = (ms.value, cnt.value)
-        return res
-
 
 class PgmBpdnHandle(BpdnHandle):
     """Owner of one device-side pgm.bpdn BPDN / WeightedBPDN problem (sporco_amd_bpdn_pgm_*): a
@@ -1701,56 +1557,42 @@ class PgmBpdnHandle(BpdnHandle):
 
     def step(self, params, read=True):
         """The phases ``params`` asks for and the reduction; the ``PGMB_*`` sums, or None without ``read``."""
-        if not read:
-            check(self._lib.sporco_amd_bpdn_pgm_step(self._h, ctypes.byref(params), None))
-            return None
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_bpdn_pgm_step(self._h, ctypes.byref(params), out))
-        return list(out)
+        if read:
+            return self._sums(self._lib.sporco_amd_bpdn_pgm_step, ctypes.byref(params))
+        check(self._lib.sporco_amd_bpdn_pgm_step(self._h, ctypes.byref(params), None))
+        return None
 
     def ystep(self, beta, gamma=0.0, use_zz=False, advance_y=False, read=True):
         """``Y = X + gamma (ZZ - X) + beta (X - Xprv)`` as a launch of its own, into the other Y array with
         ``advance_y``; ``out[PGMB_RS2] = ||X - Y||^2``, or None without ``read``."""
-        out = (ctypes.c_double * OUT_COUNT)() if read else None
-        check(self._lib.sporco_amd_bpdn_pgm_ystep(self._h, float(beta), float(gamma), int(bool(use_zz)),
-                                                  int(bool(advance_y)), out))
-        return list(out) if read else None
+        args = (float(beta), float(gamma), int(bool(use_zz)), int(bool(advance_y)))
+        if read:
+            return self._sums(self._lib.sporco_amd_bpdn_pgm_ystep, *args)
+        check(self._lib.sporco_amd_bpdn_pgm_ystep(self._h, *args, None))
+        return None
 
     def copy(self, dst, src):
         check(self._lib.sporco_amd_bpdn_pgm_copy(self._h, int(dst), int(src)))
 
 
-class CmodHandle(object):
+class CmodHandle(_Handle):
     """Owner of one device-side CnstrMOD problem (sporco_amd_cmod_*): Z (M, K) and S (N, K), host arrays that are
     copied or :class:`sporco_amd.device.DeviceArray` that are read in place (the handle keeps them alive);
     X / Y / U (N, M), host arrays in and out."""
 
+    _prefix = 'sporco_amd_cmod'
     _create = 'sporco_amd_cmod_create'
 
     def __init__(self, N, M, K, dtype, device=0, stream=None):
         self.dims = (int(N), int(M), int(K))
         self.dtype = np.dtype(dtype)
-        h = ctypes.c_void_p()
-        check(getattr(lib(), self._create)(dtype_code(dtype), int(N), int(M), int(K), int(device),
-                                           ctypes.c_void_p(stream or 0), ctypes.byref(h)))
-        self._h = h
-        self._lib = lib()
+        self._open(getattr(lib(), self._create), dtype_code(dtype), int(N), int(M), int(K), int(device),
+                   ctypes.c_void_p(stream or 0))
         self._keep = {}
 
     def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sporco_amd_cmod_destroy(self._h)
-            self._h = None
-            self._keep = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sync(self):
-        check(self._lib.sporco_amd_cmod_sync(self._h))
+        _Handle.close(self)
+        self._keep = {}
 
     def plan(self):
         """``dict(KS, slab, slabs, row_blocks, col_blocks, mfma, lds_gram, lds_iter)``: the columns of K staged per
@@ -1808,29 +1650,11 @@ class CmodHandle(object):
         return out
 
     def iter(self, params):
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_cmod_iter(self._h, ctypes.byref(params), out))
-        return list(out)
+        return self._sums(self._lib.sporco_amd_cmod_iter, ctypes.byref(params))
 
     def dfid(self, var):
         """``||V Z - S||^2`` for V = X or Y."""
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_cmod_dfid(self._h, int(var), out))
-        return out[OUT_DFID]
-
-    def profile(self, enable):
-        check(self._lib.sporco_amd_cmod_profile(self._h, 1 if enable else 0))
-
-    def profile_read(self):
-        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
-        res = {}
-        for slot in range(self._lib.sporco_amd_profile_slots()):
-            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
-            check(self._lib.sporco_amd_cmod_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
-                                                         ctypes.byref(cnt)))
-            if cnt.value:
-                res[name.value.decode()] = (ms.value, cnt.value)
-        return res
+        return self._sums(self._lib.sporco_amd_cmod_dfid, int(var))[OUT_DFID]
 
 
 class PgmCmodHandle(CmodHandle):
@@ -1862,49 +1686,35 @@ class PgmCmodHandle(CmodHandle):
     def step(self, params, read=True):
         """The phases ``params`` asks for and, with ``params.finalize``, the reduction; the ``PGMC_*`` sums, or None
         without ``read``."""
-        if not read:
-            check(self._lib.sporco_amd_cmod_pgm_step(self._h, ctypes.byref(params), None))
-            return None
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_cmod_pgm_step(self._h, ctypes.byref(params), out))
-        return list(out)
+        if read:
+            return self._sums(self._lib.sporco_amd_cmod_pgm_step, ctypes.byref(params))
+        check(self._lib.sporco_amd_cmod_pgm_step(self._h, ctypes.byref(params), None))
+        return None
 
     def dfid(self):
         """``sum W (X Z - S)^2`` of the iterate."""
         return CmodHandle.dfid(self, CMOD_X)
 
 
-class RpcaHandle(object):
+class RpcaHandle(_Handle):
     """Owner of one device-side RobustPCA problem (sporco_amd_rpca_*), also the short-lived engine of
     ``prox.prox_nuclear`` / ``prox.norm_nuclear``: S (R, C), a host array that is copied or a
     :class:`sporco_amd.device.DeviceArray` that is read in place (the handle keeps it alive); X / Y / U (R, C), host
     arrays in and out, or views of the handle's buffers (:meth:`device_view`)."""
 
+    _prefix = 'sporco_amd_rpca'
+
     def __init__(self, R, C, dtype, device=0, stream=None):
         self.dims = (int(R), int(C))
         self.n = min(self.dims)
         self.dtype = np.dtype(dtype)
-        h = ctypes.c_void_p()
-        check(lib().sporco_amd_rpca_create(dtype_code(dtype), int(R), int(C), int(device),
-                                           ctypes.c_void_p(stream or 0), ctypes.byref(h)))
-        self._h = h
-        self._lib = lib()
+        self._open(lib().sporco_amd_rpca_create, dtype_code(dtype), int(R), int(C), int(device),
+                   ctypes.c_void_p(stream or 0))
         self._keep = None
 
     def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sporco_amd_rpca_destroy(self._h)
-            self._h = None
-            self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sync(self):
-        check(self._lib.sporco_amd_rpca_sync(self._h))
+        _Handle.close(self)
+        self._keep = None
 
     def plan(self):
         """``dict(KS, slab, slabs, blocks, KB, workgroups, mfma_gram, mfma_iter, lds_gram, lds_iter)``: the positions
@@ -1962,29 +1772,12 @@ class RpcaHandle(object):
         return T
 
     def iter(self, params, T):
-        T = self._t(T)
-        out = (ctypes.c_double * OUT_COUNT)()
-        check(self._lib.sporco_amd_rpca_iter(self._h, ctypes.byref(params), _ptr(T), out))
-        return list(out)
+        return self._sums(self._lib.sporco_amd_rpca_iter, ctypes.byref(params), _ptr(self._t(T)))
 
     def apply(self, T):
         """X <- S T (R >= C) or T S."""
         T = self._t(T)
         check(self._lib.sporco_amd_rpca_apply(self._h, _ptr(T)))
-
-    def profile(self, enable):
-        check(self._lib.sporco_amd_rpca_profile(self._h, 1 if enable else 0))
-
-    def profile_read(self):
-        """``{kernel: (total ms, launches)}`` since the last read, for the slots that ran."""
-        res = {}
-        for slot in range(self._lib.sporco_amd_profile_slots()):
-            name, ms, cnt = ctypes.c_char_p(), ctypes.c_double(0.0), ctypes.c_int64(0)
-            check(self._lib.sporco_amd_rpca_profile_read(self._h, slot, ctypes.byref(name), ctypes.byref(ms),
-                                                         ctypes.byref(cnt)))
-            if cnt.value:
-                res[name.value.decode()] = (ms.value, cnt.value)
-        return res
 
 
 def dct2(a, out=None, inverse=False):

@@ -1,12 +1,10 @@
 // api_bpdn.inc -- the handle of BPDN / BPDNJoint / ElasticNet (sporco/admm/bpdn.py:24-748); kernels: csc_bpdn.h.
-// Like api_spline.inc it is included by csc_api.hip at namespace scope.  S is (N, K); X, Y, U, D^T S, the weight,
+// It is included by csc_api.hip at namespace scope; the stream, the sums, the profiler and the ownership of every
+// buffer are SideBase's (csc_impl.h).  S is (N, K); X, Y, U, D^T S, the weight,
 // Z and the saved right-hand side are (M, K), all row-major as NumPy has them.  The dictionary and the solve
 // matrix P = (D^T D + c I)^-1 come from the host in the handle's precision; the handle keeps them k-major and zero
 // padded, as bpdn_product reads them.
 template <typename T> struct Bpdn : BpdnBase {
-    int device;
-    hipStream_t st = nullptr;
-    bool own_stream = false;
     const int N, M, KB;
     const int64_t K;
     int form;                       // BPDN_FORM_MFMA: float32 on the device unless SPORCO_AMD_BPDN_PLAIN is set
@@ -14,12 +12,11 @@ template <typename T> struct Bpdn : BpdnBase {
     T *s = nullptr, *dts = nullptr, *x = nullptr, *y = nullptr, *u = nullptr, *z = nullptr, *bsave = nullptr, *wl1 = nullptr;
     T *pk = nullptr, *dk = nullptr, *dtk = nullptr, *rowf = nullptr;
     bool have_wl1 = false, have_s = false, have_d = false, have_p = false;
-    double *part = nullptr, *part_lsc = nullptr, *rowp = nullptr, *rowpx = nullptr, *out_dev = nullptr, *out_pinned = nullptr;
+    double *part = nullptr, *part_lsc = nullptr, *rowp = nullptr, *rowpx = nullptr;
     std::vector<T> stage;
 
     Bpdn(int N_, int M_, int64_t K_, int dev, void *stream)
-        : device(dev), N(N_), M(M_), KB(bpdn_kb<T>(M_, N_)), K(K_) {
-        SA_HIP(hipSetDevice(device));
+        : BpdnBase(dev, stream), N(N_), M(M_), KB(bpdn_kb<T>(M_, N_)), K(K_) {
 #ifdef SPORCO_AMD_HOSTSIM
         form = BPDN_FORM_PLAIN;
 #else
@@ -30,47 +27,15 @@ template <typename T> struct Bpdn : BpdnBase {
         M16 = bpdn_up(M, 16);
         N16 = bpdn_up(N, 16);
         nb = bpdn_blocks(K, KB);
-        try {
-            if (stream) {
-                st = (hipStream_t)stream;
-            } else {
-                SA_HIP(hipStreamCreate(&st));
-                own_stream = true;
-            }
-            prof.st = st;
-            const size_t E = sizeof(T) * (size_t)M * K;
-            SA_HIP(hipMalloc((void **)&s, sizeof(T) * (size_t)N * K));
-            SA_HIP(hipMemsetAsync(s, 0, sizeof(T) * (size_t)N * K, st));
-            for (T **p : {&dts, &x, &y, &u}) {
-                SA_HIP(hipMalloc((void **)p, E));
-                SA_HIP(hipMemsetAsync(*p, 0, E, st));
-            }
-            SA_HIP(hipMalloc((void **)&pk, sizeof(T) * (size_t)M4 * M16));
-            SA_HIP(hipMalloc((void **)&dk, sizeof(T) * (size_t)N4 * M16));
-            SA_HIP(hipMalloc((void **)&dtk, sizeof(T) * (size_t)M4 * N16));
-            SA_HIP(hipMalloc((void **)&part, sizeof(double) * kBpdnSums * nb));
-            SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
-            SA_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOutSlots, st));
-            SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
-            sync();
-        } catch (...) {
-            release();
-            throw;
-        }
+        s = dev_alloc<T>((size_t)N * K, true);
+        for (T **p : {&dts, &x, &y, &u}) need(p);
+        pk = dev_alloc<T>((size_t)M4 * M16, false);
+        dk = dev_alloc<T>((size_t)N4 * M16, false);
+        dtk = dev_alloc<T>((size_t)M4 * N16, false);
+        part = dev_alloc<double>((size_t)kBpdnSums * nb, false);
+        sync();
     }
-    void release() {
-        (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)s, (void *)dts, (void *)x, (void *)y, (void *)u, (void *)z, (void *)bsave, (void *)wl1,
-                        (void *)pk, (void *)dk, (void *)dtk, (void *)rowf, (void *)part, (void *)part_lsc, (void *)rowp,
-                        (void *)rowpx, (void *)out_dev})
-            if (p) (void)hipFree(p);
-        if (out_pinned) (void)hipHostFree(out_pinned);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-    }
-    ~Bpdn() override { release(); }
 
-    void sync() override { SA_HIP(hipStreamSynchronize(st)); }
     void plan(int64_t out[4]) override {
         out[0] = KB;
         out[1] = nb;
@@ -80,9 +45,7 @@ template <typename T> struct Bpdn : BpdnBase {
 
     // an (M, K) array made on first use, zeroed
     void need(T **p) {
-        if (*p) return;
-        SA_HIP(hipMalloc((void **)p, sizeof(T) * (size_t)M * K));
-        SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * (size_t)M * K, st));
+        if (!*p) *p = dev_alloc<T>((size_t)M * K, true);
     }
 
     BpdnArgs<T> args() {
@@ -170,12 +133,6 @@ template <typename T> struct Bpdn : BpdnBase {
         SA_HIP(hipMemcpyAsync(dst, src, var_bytes(var), hipMemcpyDeviceToHost, st));
         sync();
     }
-    void read_out(double *out_host) {
-        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
-        sync();
-        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
-    }
-
     void iter(const sporco_amd_bpdn_params &p, double *out_host) override {
         SA_REQUIRE(have_s && have_d && have_p, "bpdn: S, the dictionary and the solve matrix are set before the first iteration");
         SA_REQUIRE(p.rho > 0.0 && p.c > 0.0, "rho must be positive");
@@ -194,14 +151,14 @@ template <typename T> struct Bpdn : BpdnBase {
         a.want_x = (p.want_x || p.lin_solve_check || p.joint) ? 1 : 0;
         if (p.lin_solve_check) {
             need(&bsave);
-            if (!part_lsc) SA_HIP(hipMalloc((void **)&part_lsc, sizeof(double) * kBpdnLscSums * nb));
+            if (!part_lsc) part_lsc = dev_alloc<double>((size_t)kBpdnLscSums * nb, false);
             a.bsave = bsave;
         }
         if (p.joint) {
             need(&z);
-            if (!rowp) SA_HIP(hipMalloc((void **)&rowp, sizeof(double) * (size_t)M * nb));
-            if (!rowf) SA_HIP(hipMalloc((void **)&rowf, sizeof(T) * M));
-            if (!p.geval_y && !rowpx) SA_HIP(hipMalloc((void **)&rowpx, sizeof(double) * (size_t)M * nb));
+            if (!rowp) rowp = dev_alloc<double>((size_t)M * nb, false);
+            if (!rowf) rowf = dev_alloc<T>(M, false);
+            if (!p.geval_y && !rowpx) rowpx = dev_alloc<double>((size_t)M * nb, false);
             a.z = z;
             a.rowp = rowp;
             a.rowf = rowf;

@@ -1,12 +1,9 @@
-// api_cmod.inc -- the handle of CnstrMOD (sporco/admm/cmod.py:21-342); kernels: csc_cmod.h.  Like api_bpdn.inc it is
-// included by csc_api.hip at namespace scope.  Z is (M, K), S (N, K), row-major as NumPy has them: either the
+// api_cmod.inc -- the handle of CnstrMOD (sporco/admm/cmod.py:21-342); kernels: csc_cmod.h.  It is included by
+// csc_api.hip at namespace scope and keeps its stream, sums and buffers through SideBase (csc_impl.h).  Z is (M, K), S (N, K), row-major as NumPy has them: either the
 // handle's own copy of a host array or a device pointer read in place.  X, Y, U, S Z^T and the right-hand side are
 // (N, M) to the host; the handle keeps them k-major and zero padded, [M4][N16], as bpdn_product reads a left
 // operand.  The solve matrix Q = (Z Z^T + rho I)^-1 comes from the host in the handle's precision.
 template <typename T> struct Cmod : CmodBase {
-    int device;
-    hipStream_t st = nullptr;
-    bool own_stream = false;
     const int N, M;
     const int64_t K;
     const CmodPlan pl;
@@ -15,14 +12,14 @@ template <typename T> struct Cmod : CmodBase {
     T *s_own = nullptr, *z_own = nullptr;
     const T *s = nullptr, *z = nullptr;
     T *part_g = nullptr, *sztk = nullptr, *bk = nullptr, *xk = nullptr, *yk = nullptr, *uk = nullptr, *q = nullptr;
-    double *g = nullptr, *sztd = nullptr, *part = nullptr, *part_d = nullptr, *out_dev = nullptr, *out_pinned = nullptr;
+    double *g = nullptr, *sztd = nullptr, *part = nullptr, *part_d = nullptr;
     bool have_q = false;
     std::vector<T> stage;
 
     size_t kmaj() const { return (size_t)pl.M4 * pl.N16; }
 
-    Cmod(int N_, int M_, int64_t K_, int dev, void *stream) : device(dev), N(N_), M(M_), K(K_), pl(cmod_plan(N_, M_, K_)) {
-        SA_HIP(hipSetDevice(device));
+    Cmod(int N_, int M_, int64_t K_, int dev, void *stream)
+        : CmodBase(dev, stream), N(N_), M(M_), K(K_), pl(cmod_plan(N_, M_, K_)) {
 #ifdef SPORCO_AMD_HOSTSIM
         form = BPDN_FORM_PLAIN;
 #else
@@ -31,48 +28,16 @@ template <typename T> struct Cmod : CmodBase {
         KB = bpdn_kb<T>(M, N);
         nb_dfid = bpdn_blocks(K, KB);
         nb_iter = pl.M16 / 16;
-        try {
-            if (stream) {
-                st = (hipStream_t)stream;
-            } else {
-                SA_HIP(hipStreamCreate(&st));
-                own_stream = true;
-            }
-            prof.st = st;
-            for (T **p : {&sztk, &bk, &xk, &yk, &uk}) {
-                SA_HIP(hipMalloc((void **)p, sizeof(T) * kmaj()));
-                SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * kmaj(), st));
-            }
-            SA_HIP(hipMalloc((void **)&q, sizeof(T) * (size_t)M * M));
-            SA_HIP(hipMalloc((void **)&part_g,
-                             sizeof(T) * (size_t)pl.nsplit * pl.RB * kCmodBlk * pl.CB * kCmodBlk));
-            SA_HIP(hipMalloc((void **)&g, sizeof(double) * (size_t)M * M));
-            SA_HIP(hipMalloc((void **)&sztd, sizeof(double) * (size_t)N * M));
-            SA_HIP(hipMemsetAsync(g, 0, sizeof(double) * (size_t)M * M, st));
-            SA_HIP(hipMemsetAsync(sztd, 0, sizeof(double) * (size_t)N * M, st));
-            SA_HIP(hipMalloc((void **)&part, sizeof(double) * kCmodSums * nb_iter));
-            SA_HIP(hipMalloc((void **)&part_d, sizeof(double) * nb_dfid));
-            SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
-            SA_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOutSlots, st));
-            SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
-            sync();
-        } catch (...) {
-            release();
-            throw;
-        }
+        for (T **p : {&sztk, &bk, &xk, &yk, &uk}) *p = dev_alloc<T>(kmaj(), true);
+        q = dev_alloc<T>((size_t)M * M, false);
+        part_g = dev_alloc<T>((size_t)pl.nsplit * pl.RB * kCmodBlk * pl.CB * kCmodBlk, false);
+        g = dev_alloc<double>((size_t)M * M, true);
+        sztd = dev_alloc<double>((size_t)N * M, true);
+        part = dev_alloc<double>((size_t)kCmodSums * nb_iter, false);
+        part_d = dev_alloc<double>(nb_dfid, false);
+        sync();
     }
-    void release() {
-        (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)s_own, (void *)z_own, (void *)part_g, (void *)sztk, (void *)bk, (void *)xk, (void *)yk,
-                        (void *)uk, (void *)q, (void *)g, (void *)sztd, (void *)part, (void *)part_d, (void *)out_dev})
-            if (p) (void)hipFree(p);
-        if (out_pinned) (void)hipHostFree(out_pinned);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-    }
-    ~Cmod() override { release(); }
 
-    void sync() override { SA_HIP(hipStreamSynchronize(st)); }
     void plan(int64_t out[8]) override {
         out[0] = kCmodKS;
         out[1] = pl.slab;
@@ -92,9 +57,8 @@ template <typename T> struct Cmod : CmodBase {
             *use = (const T *)src;
             return;
         }
-        const size_t bytes = sizeof(T) * (size_t)rows * K;
-        if (!*own) SA_HIP(hipMalloc((void **)own, bytes));
-        SA_HIP(hipMemcpyAsync(*own, src, bytes, hipMemcpyHostToDevice, st));
+        if (!*own) *own = dev_alloc<T>((size_t)rows * K, false);
+        SA_HIP(hipMemcpyAsync(*own, src, sizeof(T) * (size_t)rows * K, hipMemcpyHostToDevice, st));
         sync();      // (the source may be pageable host memory)
         *use = *own;
     }
@@ -172,12 +136,6 @@ template <typename T> struct Cmod : CmodBase {
         for (int n = 0; n < N; ++n)
             for (int m = 0; m < M; ++m) h[(size_t)n * M + m] = stage[(size_t)m * pl.N16 + n];
     }
-    void read_out(double *out_host) {
-        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
-        sync();
-        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
-    }
-
     void launch_dfid(const T *fk) {
         CmodDfidArgs<T> d;
         d.fk = fk;

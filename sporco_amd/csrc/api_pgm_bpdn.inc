@@ -11,23 +11,9 @@ template <typename T> struct PgmBpdn : Bpdn<T> {
     double *part_pgm = nullptr, *part_y = nullptr;
 
     PgmBpdn(int N_, int M_, int64_t K_, int dev, void *stream) : B(N_, M_, K_, dev, stream) {
-        try {
-            SA_HIP(hipMalloc((void **)&part_pgm, sizeof(double) * kPgmBpdnSums * this->nb));
-            SA_HIP(hipMalloc((void **)&part_y, sizeof(double) * kBpdnMaxBlocks));
-        } catch (...) {
-            release_pgm();
-            throw;      // (the base class's destructor frees the rest)
-        }
+        part_pgm = this->template dev_alloc<double>((size_t)kPgmBpdnSums * this->nb, false);
+        part_y = this->template dev_alloc<double>(kBpdnMaxBlocks, false);
     }
-    void release_pgm() {
-        (void)hipSetDevice(this->device);
-        if (this->st) (void)hipStreamSynchronize(this->st);
-        for (void *p : {(void *)y2, (void *)g, (void *)zv, (void *)zz, (void *)w, (void *)part_pgm, (void *)part_y})
-            if (p) (void)hipFree(p);
-        y2 = g = zv = zz = w = nullptr;
-        part_pgm = part_y = nullptr;
-    }
-    ~PgmBpdn() override { release_pgm(); }
 
     void plan(int64_t out[4]) override {
         B::plan(out);
@@ -66,7 +52,7 @@ template <typename T> struct PgmBpdn : Bpdn<T> {
         if (var == SPORCO_AMD_BPDN_W) {
             have_w = src != nullptr;
             if (!have_w) return;
-            if (!w) SA_HIP(hipMalloc((void **)&w, var_bytes(var)));
+            if (!w) w = this->template dev_alloc<T>((size_t)this->N * this->K, false);
         }
         B::upload(var, src);
     }

@@ -18,32 +18,14 @@ template <typename T> struct PgmCmod : Cmod<T> {
 
     PgmCmod(int N_, int M_, int64_t K_, int dev, void *stream)
         : B(N_, M_, K_, dev, stream), pp(pgm_cmod_plan(N_, M_, K_)) {
-        try {
-            rows = pp.NRB * pp.nsplit;
-            rows = std::max(rows, pgm_cmod_reduce_blocks(this->M, pp.N16));
-            rows = std::max(rows, std::max(this->nb_dfid, this->nb_iter));
-            SA_HIP(hipMalloc((void **)&table, sizeof(double) * kPgmCmodSums * rows));
-            SA_HIP(hipMemsetAsync(table, 0, sizeof(double) * kPgmCmodSums * rows, this->st));
-            SA_HIP(hipMalloc((void **)&part_pg, sizeof(T) * (size_t)pp.nsplit * pp.M16 * pp.N16));
-            for (T **p : {&zv, &zz}) {
-                SA_HIP(hipMalloc((void **)p, sizeof(T) * this->kmaj()));
-                SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * this->kmaj(), this->st));
-            }
-            this->sync();
-        } catch (...) {
-            release_pgm();
-            throw;      // (the base class's destructor frees the rest)
-        }
+        rows = pp.NRB * pp.nsplit;
+        rows = std::max(rows, pgm_cmod_reduce_blocks(this->M, pp.N16));
+        rows = std::max(rows, std::max(this->nb_dfid, this->nb_iter));
+        table = this->template dev_alloc<double>((size_t)kPgmCmodSums * rows, true);
+        part_pg = this->template dev_alloc<T>((size_t)pp.nsplit * pp.M16 * pp.N16, false);
+        for (T **p : {&zv, &zz}) *p = this->template dev_alloc<T>(this->kmaj(), true);
+        this->sync();
     }
-    void release_pgm() {
-        (void)hipSetDevice(this->device);
-        if (this->st) (void)hipStreamSynchronize(this->st);
-        for (void *p : {(void *)zv, (void *)zz, (void *)part_pg, (void *)w_own, (void *)table})
-            if (p) (void)hipFree(p);
-        zv = zz = part_pg = w_own = nullptr;
-        table = nullptr;
-    }
-    ~PgmCmod() override { release_pgm(); }
 
     void plan(int64_t out[8]) override {
         out[0] = kCmodKS;

@@ -1,26 +1,23 @@
 // api_rpca.inc -- the handle of RobustPCA (sporco/admm/rpca.py:23-262) and of the stateless prox_nuclear /
-// norm_nuclear; kernels: csc_rpca.h.  Like api_cmod.inc it is included by csc_api.hip at namespace scope.  S, X, Y, U
+// norm_nuclear; kernels: csc_rpca.h.  It is included by csc_api.hip at namespace scope and keeps its stream, sums and buffers
+// through SideBase (csc_impl.h).  S, X, Y, U
 // are (R, C), row-major as NumPy has them, and stay so on the device: S either the handle's own copy of a host array
 // or a device pointer read in place.  The Gram matrix goes to the host in double; T = W diag(f) W^T comes back in
 // double and is laid out zero padded, [n4][n16], in the handle's precision (T is symmetric: that is k-major).
 template <typename T> struct Rpca : RpcaBase {
-    int device;
-    hipStream_t st = nullptr;
-    bool own_stream = false;
     const int R, C;
     const RpcaPlan pl;
     int form_gram, form_iter;       // BPDN_FORM_MFMA on the device unless SPORCO_AMD_RPCA_PLAIN is set (iter: float32 only)
     T *s_own = nullptr;
     const T *s = nullptr;
     T *x = nullptr, *y = nullptr, *u = nullptr, *tk = nullptr;
-    double *part_g = nullptr, *g = nullptr, *part = nullptr, *part_s = nullptr, *out_dev = nullptr, *out_pinned = nullptr;
+    double *part_g = nullptr, *g = nullptr, *part = nullptr, *part_s = nullptr;
     std::vector<T> stage;
 
     size_t count() const { return (size_t)R * C; }
     size_t tk_count() const { return (size_t)pl.n4 * pl.n16; }
 
-    Rpca(int R_, int C_, int dev, void *stream) : device(dev), R(R_), C(C_), pl(rpca_plan<T>(R_, C_)) {
-        SA_HIP(hipSetDevice(device));
+    Rpca(int R_, int C_, int dev, void *stream) : RpcaBase(dev, stream), R(R_), C(C_), pl(rpca_plan<T>(R_, C_)) {
 #ifdef SPORCO_AMD_HOSTSIM
         form_gram = form_iter = BPDN_FORM_PLAIN;
 #else
@@ -28,47 +25,16 @@ template <typename T> struct Rpca : RpcaBase {
         form_gram = plain ? BPDN_FORM_PLAIN : BPDN_FORM_MFMA;
         form_iter = (sizeof(T) == 4 && !plain) ? BPDN_FORM_MFMA : BPDN_FORM_PLAIN;
 #endif
-        try {
-            if (stream) {
-                st = (hipStream_t)stream;
-            } else {
-                SA_HIP(hipStreamCreate(&st));
-                own_stream = true;
-            }
-            prof.st = st;
-            for (T **p : {&x, &y, &u}) {
-                SA_HIP(hipMalloc((void **)p, sizeof(T) * count()));
-                SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * count(), st));
-            }
-            SA_HIP(hipMalloc((void **)&tk, sizeof(T) * tk_count()));
-            SA_HIP(hipMemsetAsync(tk, 0, sizeof(T) * tk_count(), st));
-            const size_t ldp = (size_t)pl.NB * kRpcaBlk;
-            SA_HIP(hipMalloc((void **)&part_g, sizeof(double) * (size_t)pl.nsplit * ldp * ldp));
-            SA_HIP(hipMalloc((void **)&g, sizeof(double) * (size_t)pl.n * pl.n));
-            SA_HIP(hipMemsetAsync(g, 0, sizeof(double) * (size_t)pl.n * pl.n, st));
-            SA_HIP(hipMalloc((void **)&part, sizeof(double) * kRpcaSums * pl.nb_iter));
-            SA_HIP(hipMalloc((void **)&part_s, sizeof(double) * 1024));
-            SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
-            SA_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOutSlots, st));
-            SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
-            sync();
-        } catch (...) {
-            release();
-            throw;
-        }
+        for (T **p : {&x, &y, &u}) *p = dev_alloc<T>(count(), true);
+        tk = dev_alloc<T>(tk_count(), true);
+        const size_t ldp = (size_t)pl.NB * kRpcaBlk;
+        part_g = dev_alloc<double>((size_t)pl.nsplit * ldp * ldp, false);
+        g = dev_alloc<double>((size_t)pl.n * pl.n, true);
+        part = dev_alloc<double>((size_t)kRpcaSums * pl.nb_iter, false);
+        part_s = dev_alloc<double>(1024, false);
+        sync();
     }
-    void release() {
-        (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)s_own, (void *)x, (void *)y, (void *)u, (void *)tk, (void *)part_g, (void *)g, (void *)part,
-                        (void *)part_s, (void *)out_dev})
-            if (p) (void)hipFree(p);
-        if (out_pinned) (void)hipHostFree(out_pinned);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-    }
-    ~Rpca() override { release(); }
 
-    void sync() override { SA_HIP(hipStreamSynchronize(st)); }
     void plan(int64_t out[10]) override {
         out[0] = kRpcaKS;
         out[1] = pl.slab;
@@ -88,7 +54,7 @@ template <typename T> struct Rpca : RpcaBase {
             sync();      // (no launch of this handle still reads the array in use)
             s = (const T *)S;
         } else {
-            if (!s_own) SA_HIP(hipMalloc((void **)&s_own, sizeof(T) * count()));
+            if (!s_own) s_own = dev_alloc<T>(count(), false);
             SA_HIP(hipMemcpyAsync(s_own, S, sizeof(T) * count(), hipMemcpyHostToDevice, st));
             sync();      // (the source may be pageable host memory)
             s = s_own;
@@ -119,12 +85,6 @@ template <typename T> struct Rpca : RpcaBase {
         SA_HIP(hipMemcpyAsync(dst, buf(var), sizeof(T) * count(), hipMemcpyDeviceToHost, st));
         sync();
     }
-    void read_out(double *out_host) {
-        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
-        sync();
-        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
-    }
-
     void gram(int mode, double u_scale, double *G_host) override {
         SA_REQUIRE(s != nullptr, "rpca: S is set first");
         SA_REQUIRE(G_host != nullptr, "rpca: null destination");

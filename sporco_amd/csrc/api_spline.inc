@@ -1,12 +1,8 @@
 // api_spline.inc -- the handle of SplineL1 (sporco/admm/spline.py:24-291); kernels: csc_spline.h, transforms:
 // rfft2 / irfft2 of fft.h on the generic chain.  Like api_tvdc.inc it is included by csc_api.hip at namespace
-// scope, below template Csc<T>.  S, Y, U and the weight are (H, W, P) arrays in their natural order; XV, RY, RU are
+// scope, below template Csc<T>, and keeps its stream, sums, plans and buffers through SideBase.  S, Y, U and the weight are (H, W, P) arrays in their natural order; XV, RY, RU are
 // the same size in the DCT's permuted order (csc_spline.h); the work spectrum is (H, Wf, P).
 template <typename T> struct Spl : SplBase {
-    int device;
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    FftPlan planH, planW;
     const int H, W, Wf;
     const int64_t P;
     int64_t E;                      // H W P
@@ -15,60 +11,27 @@ template <typename T> struct Spl : SplBase {
     cx<T> *wf = nullptr;
     bool have_wdf = false, have_s = false;
     int sblocks = 1, yblocks = 1, solve_vals = 0;
-    double *part_y = nullptr, *part_s = nullptr, *out_dev = nullptr, *out_pinned = nullptr;
+    double *part_y = nullptr, *part_s = nullptr;
 
-    Spl(int H_, int W_, int64_t P_, int dev, void *stream) : device(dev), H(H_), W(W_), Wf(W_ / 2 + 1), P(P_) {
-        SA_HIP(hipSetDevice(device));
+    Spl(int H_, int W_, int64_t P_, int dev, void *stream) : SplBase(dev, stream), H(H_), W(W_), Wf(W_ / 2 + 1), P(P_) {
         E = (int64_t)H * W * P;
-        try {
-            planH.init(H);
-            planW.init(W);
-            // (the refusal of a line that does not fit a workgroup's LDS comes here, not at the first iteration)
-            fft_require_line_fits<T>(planW);
-            fft_require_line_fits<T>(planH);
-            if (stream) {
-                st = (hipStream_t)stream;
-            } else {
-                SA_HIP(hipStreamCreate(&st));
-                own_stream = true;
-            }
-            prof.st = st;
-            for (T **p : {&s, &x, &xv, &y, &u, &ry, &ru}) {
-                SA_HIP(hipMalloc((void **)p, sizeof(T) * E));
-                SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * E, st));
-            }
-            SA_HIP(hipMalloc((void **)&wf, sizeof(cx<T>) * H * Wf * P));
-            SA_HIP(hipMemsetAsync(wf, 0, sizeof(cx<T>) * H * Wf * P, st));
-            SA_HIP(hipMalloc((void **)&th, sizeof(SplTab<T>) * H));
-            SA_HIP(hipMalloc((void **)&tw, sizeof(SplTab<T>) * W));
-            launch_spl_tables<T>(st, H, W, th, tw);
-            sblocks = spl_solve_blocks(solve_args(T(1)));
-            yblocks = kSplMaxBlocks;      // (spl_ystep and, when S is set, spl_sumsq leave their partials here)
-            SA_HIP(hipMalloc((void **)&part_y, sizeof(double) * kSplYstepSums * yblocks));
-            SA_HIP(hipMalloc((void **)&part_s, sizeof(double) * kSplSolveSums * sblocks));
-            SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
-            SA_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOutSlots, st));
-            SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
-            sync();
-        } catch (...) {
-            release();
-            throw;
-        }
+        planH.init(H);
+        planW.init(W);
+        // (the refusal of a line that does not fit a workgroup's LDS comes here, not at the first iteration)
+        fft_require_line_fits<T>(planW);
+        fft_require_line_fits<T>(planH);
+        for (T **p : {&s, &x, &xv, &y, &u, &ry, &ru}) *p = dev_alloc<T>(E, true);
+        wf = dev_alloc<cx<T>>((size_t)H * Wf * P, true);
+        th = dev_alloc<SplTab<T>>(H, false);
+        tw = dev_alloc<SplTab<T>>(W, false);
+        launch_spl_tables<T>(st, H, W, th, tw);
+        sblocks = spl_solve_blocks(solve_args(T(1)));
+        yblocks = kSplMaxBlocks;      // (spl_ystep and, when S is set, spl_sumsq leave their partials here)
+        part_y = dev_alloc<double>(kSplYstepSums * yblocks, false);
+        part_s = dev_alloc<double>(kSplSolveSums * sblocks, false);
+        sync();
     }
-    void release() {
-        (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)s, (void *)x, (void *)xv, (void *)y, (void *)u, (void *)ry, (void *)ru, (void *)wdf,
-                        (void *)th, (void *)tw, (void *)wf, (void *)part_y, (void *)part_s, (void *)out_dev})
-            if (p) (void)hipFree(p);
-        if (out_pinned) (void)hipHostFree(out_pinned);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-        planH.destroy();
-        planW.destroy();
-    }
-    ~Spl() override { release(); }
 
-    void sync() override { SA_HIP(hipStreamSynchronize(st)); }
     void plan(int64_t out[4]) override {
         // planes per access of the kernels (2: 16 bytes of spectrum, 8 of image in float32), row pairs of
         // spl_solve, its workgroups and those of spl_ystep
@@ -106,7 +69,7 @@ template <typename T> struct Spl : SplBase {
         if (var == SPORCO_AMD_SPL_WDF) {
             have_wdf = src != nullptr;
             if (!have_wdf) return;
-            if (!wdf) SA_HIP(hipMalloc((void **)&wdf, sizeof(T) * E));
+            if (!wdf) wdf = dev_alloc<T>(E, false);
         }
         SA_REQUIRE(src != nullptr, "spline: null source");
         SA_HIP(hipMemcpyAsync(var_buf(var), src, sizeof(T) * E, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
@@ -138,12 +101,6 @@ template <typename T> struct Spl : SplBase {
         SA_HIP(hipMemcpyAsync(dst, src, sizeof(T) * E, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
         sync();
     }
-    void read_out(double *out_host) {
-        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
-        sync();
-        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
-    }
-
     // the x step: X = idct(Gamma dct(Y + S - u_scale U)), left in the permuted order of the transform
     void xstep(const sporco_amd_spl_params &p) override {
         SA_REQUIRE(have_s, "spline: S is set before the first x step");

@@ -4,9 +4,6 @@
 // l1 mode (sporco_amd_tvl1_create): TVL1Denoise (sporco/admm/tvl1.py:27-399) -- three blocks in Y and U, no
 // dY, the y step and the adjoint are the tvl1_* kernels, the sweeps run with rho = 1 and a unit DFidWeight.
 template <typename T> struct Tvd : TvdBase {
-    int device;
-    hipStream_t st = nullptr;
-    bool own_stream = false;
     TvdPlan pl;
     const bool l1;
     const int nb;                   // blocks of Y and of U: 2, or 3 in l1 mode
@@ -15,44 +12,19 @@ template <typename T> struct Tvd : TvdBase {
     T *wdf = nullptr, *wtv = nullptr;
     bool have_wdf = false, have_wtv = false;
     int cur = 0;                    // x[cur] is X
-    double *part_a = nullptr, *part_b = nullptr, *out_dev = nullptr, *out_pinned = nullptr;
+    double *part_a = nullptr, *part_b = nullptr;
 
     Tvd(int H, int W, int64_t P, int C, bool vtv, bool l1_mode, int dev, void *stream)
-        : device(dev), l1(l1_mode), nb(l1_mode ? 3 : 2) {
-        SA_HIP(hipSetDevice(device));
+        : TvdBase(dev, stream), l1(l1_mode), nb(l1_mode ? 3 : 2) {
         pl = tvd_plan(sizeof(T), H, W, P, C, vtv);
         E = pl.L * H;
-        if (stream) {
-            st = (hipStream_t)stream;
-        } else {
-            SA_HIP(hipStreamCreate(&st));
-            own_stream = true;
-        }
-        prof.st = st;
-        for (T **p : {&s, &x[0], &x[1], &pd, &q}) alloc_zero(p, E);
-        for (T **p : {&y, &u}) alloc_zero(p, nb * E);
-        if (!l1) alloc_zero(&dy, 2 * E);
-        SA_HIP(hipMalloc((void **)&part_a, sizeof(double) * kTvdSums * pl.blocks()));
-        SA_HIP(hipMalloc((void **)&part_b, sizeof(double) * kTvdSums * pl.blocks()));
-        SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
-        SA_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOutSlots, st));
-        SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
-    }
-    void alloc_zero(T **p, int64_t n) {
-        SA_HIP(hipMalloc((void **)p, sizeof(T) * n));
-        SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * n, st));
-    }
-    ~Tvd() override {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)s, (void *)x[0], (void *)x[1], (void *)y, (void *)u, (void *)dy, (void *)pd, (void *)q,
-                        (void *)wdf, (void *)wtv, (void *)part_a, (void *)part_b, (void *)out_dev})
-            if (p) (void)hipFree(p);
-        if (out_pinned) (void)hipHostFree(out_pinned);
-        if (own_stream) (void)hipStreamDestroy(st);
+        for (T **p : {&s, &x[0], &x[1], &pd, &q}) *p = dev_alloc<T>(E, true);
+        for (T **p : {&y, &u}) *p = dev_alloc<T>(nb * E, true);
+        if (!l1) dy = dev_alloc<T>(2 * E, true);
+        part_a = dev_alloc<double>(kTvdSums * pl.blocks(), false);
+        part_b = dev_alloc<double>(kTvdSums * pl.blocks(), false);
     }
 
-    void sync() override { SA_HIP(hipStreamSynchronize(st)); }
     void plan(int64_t out[6]) override {
         out[0] = pl.cnt;
         out[1] = pl.items;
@@ -83,7 +55,7 @@ template <typename T> struct Tvd : TvdBase {
             have = src != nullptr;
             if (!have) return;
             SA_REQUIRE(var == SPORCO_AMD_TVD_WDF || !pl.vtv, "tvd: vector TV takes a scalar TVWeight");
-            if (!w) SA_HIP(hipMalloc((void **)&w, sizeof(T) * E));
+            if (!w) w = dev_alloc<T>(E, false);
         }
         SA_REQUIRE(src != nullptr, "tvd: null source");
         int64_t n;
@@ -133,12 +105,6 @@ template <typename T> struct Tvd : TvdBase {
         a.geval_y = p.geval_y;
         return a;
     }
-    void read_out(double *out_host) {
-        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
-        sync();
-        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
-    }
-
     void sweeps(const sporco_amd_tvd_params &p, int n) override {
         for (int i = 0; i < n; ++i) {
             ProfScope ps(prof, PS_TVD_SWEEP);

@@ -1,15 +1,12 @@
 // api_tvdc.inc -- the handle of TVL2Deconv (sporco/admm/tvl2.py:377-702) and, in l1 mode, TVL1Deconv
 // (sporco/admm/tvl1.py:403-758); kernels: csc_tvdc.h, transforms: rfft2 / irfft2 of fft.h on the generic
-// chain.  Like api_tvd.inc it is included by csc_api.hip at namespace scope, below template Csc<T>.
+// chain.  Like api_tvd.inc it is included by csc_api.hip at namespace scope, below template Csc<T>; the stream, the
+// sums, the profiler, the two transform plans and the ownership of every buffer are SideBase's (csc_impl.h).
 // The arrays: S, Y, U (nb blocks), dY (l2) and the weights are (H, W, P); XH, RY, RU are (H, W, NZ, P) with
 // NZ = 1 (l2) or 2 (l1); the spectra Sf, AHSf are (H, Wf, P), Af and |Af|^2 (H, Wf, PA) with PA = P (a kernel
 // per plane) or 1 (one for all), the work spectrum (H, Wf, NZ, P).
 template <typename T> struct Tvdc : TvdcBase {
-    int device;
-    hipStream_t st = nullptr;
-    bool own_stream = false;
     TvdPlan pl;
-    FftPlan planH, planW;
     const bool l1;
     const int nb, nz;               // blocks of Y and of U; planes of XH, RY, RU per image plane
     const int H, W, Wf;
@@ -20,79 +17,40 @@ template <typename T> struct Tvdc : TvdcBase {
     cx<T> *wf = nullptr, *sf = nullptr, *ahsf = nullptr, *af = nullptr;
     bool have_wdf = false, have_wtv = false, have_s = false, have_a = false;
     int sblocks = 1;
-    double *part_y = nullptr, *part_a = nullptr, *part_s = nullptr, *part_d = nullptr, *out_dev = nullptr,
-           *out_pinned = nullptr;
+    double *part_y = nullptr, *part_a = nullptr, *part_s = nullptr, *part_d = nullptr;
 
     Tvdc(int H_, int W_, int64_t P_, int C, bool vtv, bool l1_mode, int64_t PA_, int dev, void *stream)
-        : device(dev), l1(l1_mode), nb(l1_mode ? 3 : 2), nz(l1_mode ? 2 : 1), H(H_), W(W_), Wf(W_ / 2 + 1), P(P_),
-          PA(PA_) {
+        : TvdcBase(dev, stream), l1(l1_mode), nb(l1_mode ? 3 : 2), nz(l1_mode ? 2 : 1), H(H_), W(W_), Wf(W_ / 2 + 1),
+          P(P_), PA(PA_) {
         SA_REQUIRE(PA == P || PA == 1, "tvdc: one kernel for all planes or one per plane");
-        SA_HIP(hipSetDevice(device));
         pl = tvd_plan(sizeof(T), H, W, P, C, vtv);
         E = pl.L * H;
         F = (int64_t)H * Wf * P;
-        try {
-            planH.init(H);
-            planW.init(W);
-            // (the refusal of a line that does not fit a workgroup's LDS comes here, not at the first iteration)
-            fft_require_line_fits<T>(planW);
-            fft_require_line_fits<T>(planH);
-            if (stream) {
-                st = (hipStream_t)stream;
-            } else {
-                SA_HIP(hipStreamCreate(&st));
-                own_stream = true;
-            }
-            prof.st = st;
-            alloc_zero(&s, E);
-            for (T **p : {&xh, &ry, &ru}) alloc_zero(p, nz * E);
-            for (T **p : {&y, &u}) alloc_zero(p, nb * E);
-            if (!l1) alloc_zero(&dy, 2 * E);
-            alloc_zero(&aha, (int64_t)H * Wf * PA);
-            alloc_zero(&ch, H);
-            alloc_zero(&cw, Wf);
-            alloc_zero_cx(&wf, nz * F);
-            alloc_zero_cx(&sf, F);
-            alloc_zero_cx(&ahsf, F);
-            alloc_zero_cx(&af, (int64_t)H * Wf * PA);
-            launch_tvdc_tables<T>(st, H, W, ch, cw);
-            sblocks = tvdc_solve_blocks(solve_args(T(1)));
-            SA_HIP(hipMalloc((void **)&part_y, sizeof(double) * kTvdSums * pl.blocks()));
-            SA_HIP(hipMalloc((void **)&part_a, sizeof(double) * kTvdSums * pl.blocks()));
-            SA_HIP(hipMalloc((void **)&part_s, sizeof(double) * kTvdcSolveSums * sblocks));
-            SA_HIP(hipMalloc((void **)&part_d, sizeof(double) * sblocks));
-            SA_HIP(hipMalloc((void **)&out_dev, sizeof(double) * kOutSlots));
-            SA_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOutSlots, st));
-            SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
-            sync();
-        } catch (...) {
-            release();
-            throw;
-        }
+        planH.init(H);
+        planW.init(W);
+        // (the refusal of a line that does not fit a workgroup's LDS comes here, not at the first iteration)
+        fft_require_line_fits<T>(planW);
+        fft_require_line_fits<T>(planH);
+        s = dev_alloc<T>(E, true);
+        for (T **p : {&xh, &ry, &ru}) *p = dev_alloc<T>(nz * E, true);
+        for (T **p : {&y, &u}) *p = dev_alloc<T>(nb * E, true);
+        if (!l1) dy = dev_alloc<T>(2 * E, true);
+        aha = dev_alloc<T>((int64_t)H * Wf * PA, true);
+        ch = dev_alloc<T>(H, true);
+        cw = dev_alloc<T>(Wf, true);
+        wf = dev_alloc<cx<T>>(nz * F, true);
+        sf = dev_alloc<cx<T>>(F, true);
+        ahsf = dev_alloc<cx<T>>(F, true);
+        af = dev_alloc<cx<T>>((int64_t)H * Wf * PA, true);
+        launch_tvdc_tables<T>(st, H, W, ch, cw);
+        sblocks = tvdc_solve_blocks(solve_args(T(1)));
+        part_y = dev_alloc<double>(kTvdSums * pl.blocks(), false);
+        part_a = dev_alloc<double>(kTvdSums * pl.blocks(), false);
+        part_s = dev_alloc<double>(kTvdcSolveSums * sblocks, false);
+        part_d = dev_alloc<double>(sblocks, false);
+        sync();
     }
-    void alloc_zero(T **p, int64_t n) {
-        SA_HIP(hipMalloc((void **)p, sizeof(T) * n));
-        SA_HIP(hipMemsetAsync(*p, 0, sizeof(T) * n, st));
-    }
-    void alloc_zero_cx(cx<T> **p, int64_t n) {
-        SA_HIP(hipMalloc((void **)p, sizeof(cx<T>) * n));
-        SA_HIP(hipMemsetAsync(*p, 0, sizeof(cx<T>) * n, st));
-    }
-    void release() {
-        (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)s, (void *)xh, (void *)y, (void *)u, (void *)dy, (void *)ry, (void *)ru, (void *)wdf,
-                        (void *)wtv, (void *)aha, (void *)ch, (void *)cw, (void *)wf, (void *)sf, (void *)ahsf, (void *)af,
-                        (void *)part_y, (void *)part_a, (void *)part_s, (void *)part_d, (void *)out_dev})
-            if (p) (void)hipFree(p);
-        if (out_pinned) (void)hipHostFree(out_pinned);
-        if (own_stream && st) (void)hipStreamDestroy(st);
-        planH.destroy();
-        planW.destroy();
-    }
-    ~Tvdc() override { release(); }
 
-    void sync() override { SA_HIP(hipStreamSynchronize(st)); }
     void plan(int64_t out[8]) override {
         out[0] = pl.cnt;
         out[1] = pl.items;
@@ -146,7 +104,7 @@ template <typename T> struct Tvdc : TvdcBase {
             have = src != nullptr;
             if (!have) return;
             SA_REQUIRE(var == SPORCO_AMD_TVDC_WDF || !pl.vtv, "tvdc: vector TV takes a scalar TVWeight");
-            if (!w) SA_HIP(hipMalloc((void **)&w, sizeof(T) * E));
+            if (!w) w = dev_alloc<T>(E, false);
         }
         SA_REQUIRE(src != nullptr, "tvdc: null source");
         int64_t n;
@@ -226,12 +184,6 @@ template <typename T> struct Tvdc : TvdcBase {
         a.geval_y = p.geval_y;
         return a;
     }
-    void read_out(double *out_host) {
-        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
-        sync();
-        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
-    }
-
     // the x step: Xf from the right-hand side RY - u_scale RU, then X (l1: X and H X)
     void xstep(const sporco_amd_tvdc_params &p) override {
         SA_REQUIRE(have_s && have_a, "tvdc: S and the kernel A are set before the first x step");

@@ -5,6 +5,76 @@
 
 using namespace sporco_amd;
 
+// ---- what the entry points of every handle share (called between SA_API_BEGIN and SA_API_END) ------------------
+static void require_device(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
+    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+}
+
+// a live handle, its device current
+template <class H> static void check_handle(H *h) {
+    SA_REQUIRE(h != nullptr && h->impl, "null handle");
+    SA_HIP(hipSetDevice(h->device));
+}
+
+// a side handle (csc_impl.h SideHandle) around what make() returns; the family's own argument checks come first
+template <class H, class Make> static void create_handle(int device, H **out, Make make) {
+    SA_REQUIRE(out != nullptr, "null argument");
+    require_device(device);
+    std::unique_ptr<H> h(new H);
+    h->device = device;
+    h->impl.reset(make());
+    *out = h.release();
+}
+
+template <class H> static void destroy_handle(H *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+template <class H> static void sync_handle(H *h) {
+    check_handle(h);
+    h->impl->sync();
+}
+
+// timing on / off: the stream drained by the caller's sync, what is pending folded into the totals
+static void profile_enable(Profiler &pr, int enable) {
+    pr.drain();
+    // create the event pool up front: hipEventCreate is slow enough to distort a timed region if it happens
+    // lazily inside it
+    while (enable && pr.pool.size() < 512) {
+        hipEvent_t e;
+        SA_HIP(hipEventCreate(&e));
+        pr.pool.push_back(e);
+    }
+    pr.on = enable != 0;
+}
+
+// one slot's name, total and launch count since the last read
+static void profile_read(Profiler &pr, int slot, const char **name, double *total_ms, int64_t *launches) {
+    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
+    pr.drain();
+    if (name) *name = kProfNames[slot];
+    if (total_ms) *total_ms = pr.total_ms[slot];
+    if (launches) *launches = pr.count[slot];
+    pr.total_ms[slot] = 0.0;
+    pr.count[slot] = 0;
+}
+
+template <class H> static void profile_handle(H *h, int enable) {
+    sync_handle(h);
+    profile_enable(h->impl->prof, enable);
+}
+
+template <class H>
+static void profile_read_handle(H *h, int slot, const char **name, double *total_ms, int64_t *launches) {
+    check_handle(h);
+    profile_read(h->impl->prof, slot, name, total_ms, launches);
+}
+
 extern "C" {
 
 const char *sporco_amd_version(void) { return "sporco_amd 0.1.0 (gfx950)"; }
@@ -47,10 +117,7 @@ int sporco_amd_csc_create_mc(const sporco_amd_dims *dims, int32_t dict_channels,
     SA_API_BEGIN
     SA_REQUIRE(dims && out, "null argument");
     SA_REQUIRE(dict_channels >= 1, "dict_channels must be >= 1");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    require_device(device);
     std::unique_ptr<sporco_amd_csc> h(new sporco_amd_csc);
     h->device = device;
     h->impl.reset(make_csc(*dims, dict_channels, device, stream));
@@ -63,10 +130,7 @@ int sporco_amd_csc_create_volume(const sporco_amd_dims *dims, int32_t depth, int
     SA_API_BEGIN
     SA_REQUIRE(dims && out, "null argument");
     SA_REQUIRE(depth >= 1 && dims->H % depth == 0, "depth must divide the folded first axis dims->H");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
+    require_device(device);
     std::unique_ptr<sporco_amd_csc> h(new sporco_amd_csc);
     h->device = device;
     h->depth = depth;
@@ -77,17 +141,13 @@ int sporco_amd_csc_create_volume(const sporco_amd_dims *dims, int32_t depth, int
 
 int sporco_amd_csc_destroy(sporco_amd_csc_t h) {
     SA_API_BEGIN
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
+    destroy_handle(h);
     SA_API_END
 }
 
 int sporco_amd_csc_sync(sporco_amd_csc_t h) {
     SA_API_BEGIN
-    SA_HANDLE_ANY(h);
-    h->impl->sync();
+    sync_handle(h);
     SA_API_END
 }
 
@@ -804,20 +864,7 @@ int sporco_amd_csc_asum(sporco_amd_csc_t h, int var, double out[SPORCO_AMD_OUT_C
 
 int sporco_amd_csc_profile(sporco_amd_csc_t h, int enable) {
     SA_API_BEGIN
-    SA_HANDLE_ANY(h);
-    h->impl->sync();
-    h->impl->prof.drain();
-    if (enable) {
-        // create the event pool up front: hipEventCreate is slow enough to
-        // distort a timed region if it happens lazily inside it
-        Profiler &pr = h->impl->prof;
-        while (pr.pool.size() < 512) {
-            hipEvent_t e;
-            SA_HIP(hipEventCreate(&e));
-            pr.pool.push_back(e);
-        }
-    }
-    h->impl->prof.on = enable != 0;
+    profile_handle(h, enable);
     SA_API_END
 }
 
@@ -826,73 +873,43 @@ int sporco_amd_profile_slots(void) { return PS_COUNT; }
 int sporco_amd_csc_profile_read(sporco_amd_csc_t h, int slot, const char **name, double *total_ms,
                                 int64_t *launches) {
     SA_API_BEGIN
-    SA_HANDLE_ANY(h);
-    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
-    h->impl->prof.drain();
-    if (name) *name = kProfNames[slot];
-    if (total_ms) *total_ms = h->impl->prof.total_ms[slot];
-    if (launches) *launches = h->impl->prof.count[slot];
-    h->impl->prof.total_ms[slot] = 0.0;
-    h->impl->prof.count[slot] = 0;
+    profile_read_handle(h, slot, name, total_ms, launches);
     SA_API_END
 }
 
-// ---- TVL2Denoise: a handle of its own (csc_impl.h TvdBase) ----------------------------------------
-#define SA_TVD_HANDLE(h)                                                               \
-    SA_REQUIRE((h) != nullptr && (h)->impl, "null TVL2Denoise handle");                \
-    SA_HIP(hipSetDevice((h)->device));
+// ---- TVL2Denoise: a side handle (csc_impl.h TvdBase) ----------------------------------------
 
 int sporco_amd_tvd_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int device,
                           void *stream, sporco_amd_tvd_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(H >= 2 && W >= 2 && P >= 1 && C >= 1, "tvd: H, W >= 2, P, C >= 1");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_tvd> h(new sporco_amd_tvd);
-    h->device = device;
-    h->impl.reset(make_tvd(dtype, H, W, P, C, vector_tv != 0, false, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_tvd(dtype, H, W, P, C, vector_tv != 0, false, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_tvl1_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int device,
                            void *stream, sporco_amd_tvd_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(H >= 2 && W >= 2 && P >= 1 && C >= 1, "tvl1: H, W >= 2, P, C >= 1");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_tvd> h(new sporco_amd_tvd);
-    h->device = device;
-    h->impl.reset(make_tvd(dtype, H, W, P, C, vector_tv != 0, true, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_tvd(dtype, H, W, P, C, vector_tv != 0, true, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_tvd_destroy(sporco_amd_tvd_t h) {
     SA_API_BEGIN
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
+    destroy_handle(h);
     SA_API_END
 }
 
 int sporco_amd_tvd_sync(sporco_amd_tvd_t h) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
-    h->impl->sync();
+    sync_handle(h);
     SA_API_END
 }
 
 int sporco_amd_tvd_plan(sporco_amd_tvd_t h, int64_t out[6]) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     h->impl->plan(out);
     SA_API_END
@@ -900,21 +917,21 @@ int sporco_amd_tvd_plan(sporco_amd_tvd_t h, int64_t out[6]) {
 
 int sporco_amd_tvd_upload(sporco_amd_tvd_t h, int var, const void *src, int on_device) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
+    check_handle(h);
     h->impl->upload(var, src, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_tvd_download(sporco_amd_tvd_t h, int var, void *dst, int on_device) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
+    check_handle(h);
     h->impl->download(var, dst, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_tvd_sweeps(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p, int32_t n) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && n >= 0, "bad argument");
     h->impl->sweeps(*p, n);
     SA_API_END
@@ -922,7 +939,7 @@ int sporco_amd_tvd_sweeps(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p, in
 
 int sporco_amd_tvd_gsres(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
     h->impl->gsres(*p, out);
     SA_API_END
@@ -930,7 +947,7 @@ int sporco_amd_tvd_gsres(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p, dou
 
 int sporco_amd_tvd_ystep(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
     h->impl->ystep(*p, out);
     SA_API_END
@@ -938,60 +955,31 @@ int sporco_amd_tvd_ystep(sporco_amd_tvd_t h, const sporco_amd_tvd_params *p, dou
 
 int sporco_amd_tvd_adjoint(sporco_amd_tvd_t h) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
+    check_handle(h);
     h->impl->adjoint();
     SA_API_END
 }
 
 int sporco_amd_tvd_profile(sporco_amd_tvd_t h, int enable) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
-    h->impl->sync();
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (enable)
-        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
-            hipEvent_t e;
-            SA_HIP(hipEventCreate(&e));
-            pr.pool.push_back(e);
-        }
-    pr.on = enable != 0;
+    profile_handle(h, enable);
     SA_API_END
 }
 
 int sporco_amd_tvd_profile_read(sporco_amd_tvd_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
     SA_API_BEGIN
-    SA_TVD_HANDLE(h);
-    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (name) *name = kProfNames[slot];
-    if (total_ms) *total_ms = pr.total_ms[slot];
-    if (launches) *launches = pr.count[slot];
-    pr.total_ms[slot] = 0.0;
-    pr.count[slot] = 0;
+    profile_read_handle(h, slot, name, total_ms, launches);
     SA_API_END
 }
 
-// ---- TVL2Deconv / TVL1Deconv: a handle of its own (csc_impl.h TvdcBase) ---------------------------------
-#define SA_TVDC_HANDLE(h)                                                              \
-    SA_REQUIRE((h) != nullptr && (h)->impl, "null TV deconvolution handle");           \
-    SA_HIP(hipSetDevice((h)->device));
+// ---- TVL2Deconv / TVL1Deconv: a side handle (csc_impl.h TvdcBase) ---------------------------------
 
 static int tvdc_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t C, int32_t vector_tv, int64_t PA, bool l1,
                        int device, void *stream, sporco_amd_tvdc_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(H >= 2 && W >= 2 && P >= 1 && C >= 1, "tvdc: H, W >= 2, P, C >= 1");
     SA_REQUIRE(PA == P || PA == 1, "tvdc: the kernel has P planes or one");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_tvdc> h(new sporco_amd_tvdc);
-    h->device = device;
-    h->impl.reset(make_tvdc(dtype, H, W, P, C, vector_tv != 0, l1, PA, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_tvdc(dtype, H, W, P, C, vector_tv != 0, l1, PA, device, stream); });
     SA_API_END
 }
 
@@ -1007,23 +995,19 @@ int sporco_amd_tvl1dc_create(int dtype, int32_t H, int32_t W, int64_t P, int32_t
 
 int sporco_amd_tvdc_destroy(sporco_amd_tvdc_t h) {
     SA_API_BEGIN
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
+    destroy_handle(h);
     SA_API_END
 }
 
 int sporco_amd_tvdc_sync(sporco_amd_tvdc_t h) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
-    h->impl->sync();
+    sync_handle(h);
     SA_API_END
 }
 
 int sporco_amd_tvdc_plan(sporco_amd_tvdc_t h, int64_t out[8]) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     h->impl->plan(out);
     SA_API_END
@@ -1031,28 +1015,28 @@ int sporco_amd_tvdc_plan(sporco_amd_tvdc_t h, int64_t out[8]) {
 
 int sporco_amd_tvdc_upload(sporco_amd_tvdc_t h, int var, const void *src, int on_device) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
+    check_handle(h);
     h->impl->upload(var, src, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_tvdc_download(sporco_amd_tvdc_t h, int var, void *dst, int on_device) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
+    check_handle(h);
     h->impl->download(var, dst, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_tvdc_set_kernel(sporco_amd_tvdc_t h, const void *A, int32_t ah, int32_t aw, int on_device) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
+    check_handle(h);
     h->impl->set_kernel(A, ah, aw, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_tvdc_xstep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr, "null argument");
     h->impl->xstep(*p);
     SA_API_END
@@ -1060,7 +1044,7 @@ int sporco_amd_tvdc_xstep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p) 
 
 int sporco_amd_tvdc_ystep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
     h->impl->ystep(*p, out);
     SA_API_END
@@ -1068,80 +1052,47 @@ int sporco_amd_tvdc_ystep(sporco_amd_tvdc_t h, const sporco_amd_tvdc_params *p, 
 
 int sporco_amd_tvdc_adjoint(sporco_amd_tvdc_t h) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
+    check_handle(h);
     h->impl->adjoint();
     SA_API_END
 }
 
 int sporco_amd_tvdc_profile(sporco_amd_tvdc_t h, int enable) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
-    h->impl->sync();
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (enable)
-        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
-            hipEvent_t e;
-            SA_HIP(hipEventCreate(&e));
-            pr.pool.push_back(e);
-        }
-    pr.on = enable != 0;
+    profile_handle(h, enable);
     SA_API_END
 }
 
 int sporco_amd_tvdc_profile_read(sporco_amd_tvdc_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
     SA_API_BEGIN
-    SA_TVDC_HANDLE(h);
-    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (name) *name = kProfNames[slot];
-    if (total_ms) *total_ms = pr.total_ms[slot];
-    if (launches) *launches = pr.count[slot];
-    pr.total_ms[slot] = 0.0;
-    pr.count[slot] = 0;
+    profile_read_handle(h, slot, name, total_ms, launches);
     SA_API_END
 }
 
-// ---- SplineL1: a handle of its own (csc_impl.h SplBase), and the stateless DCT ----------------------------
-#define SA_SPL_HANDLE(h)                                                               \
-    SA_REQUIRE((h) != nullptr && (h)->impl, "null spline handle");                     \
-    SA_HIP(hipSetDevice((h)->device));
+// ---- SplineL1: a side handle (csc_impl.h SplBase), and the stateless DCT ----------------------------
 
 int sporco_amd_spl_create(int dtype, int32_t H, int32_t W, int64_t P, int device, void *stream, sporco_amd_spl_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(H >= 1 && W >= 2 && P >= 1, "spline: H >= 1, W >= 2, P >= 1");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_spl> h(new sporco_amd_spl);
-    h->device = device;
-    h->impl.reset(make_spl(dtype, H, W, P, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_spl(dtype, H, W, P, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_spl_destroy(sporco_amd_spl_t h) {
     SA_API_BEGIN
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
+    destroy_handle(h);
     SA_API_END
 }
 
 int sporco_amd_spl_sync(sporco_amd_spl_t h) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
-    h->impl->sync();
+    sync_handle(h);
     SA_API_END
 }
 
 int sporco_amd_spl_plan(sporco_amd_spl_t h, int64_t out[4]) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     h->impl->plan(out);
     SA_API_END
@@ -1149,21 +1100,21 @@ int sporco_amd_spl_plan(sporco_amd_spl_t h, int64_t out[4]) {
 
 int sporco_amd_spl_upload(sporco_amd_spl_t h, int var, const void *src, int on_device) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
+    check_handle(h);
     h->impl->upload(var, src, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_spl_download(sporco_amd_spl_t h, int var, void *dst, int on_device) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
+    check_handle(h);
     h->impl->download(var, dst, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_spl_xstep(sporco_amd_spl_t h, const sporco_amd_spl_params *p) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr, "null argument");
     h->impl->xstep(*p);
     SA_API_END
@@ -1171,7 +1122,7 @@ int sporco_amd_spl_xstep(sporco_amd_spl_t h, const sporco_amd_spl_params *p) {
 
 int sporco_amd_spl_ystep(sporco_amd_spl_t h, const sporco_amd_spl_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
     h->impl->ystep(*p, out);
     SA_API_END
@@ -1179,31 +1130,13 @@ int sporco_amd_spl_ystep(sporco_amd_spl_t h, const sporco_amd_spl_params *p, dou
 
 int sporco_amd_spl_profile(sporco_amd_spl_t h, int enable) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
-    h->impl->sync();
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (enable)
-        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
-            hipEvent_t e;
-            SA_HIP(hipEventCreate(&e));
-            pr.pool.push_back(e);
-        }
-    pr.on = enable != 0;
+    profile_handle(h, enable);
     SA_API_END
 }
 
 int sporco_amd_spl_profile_read(sporco_amd_spl_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
     SA_API_BEGIN
-    SA_SPL_HANDLE(h);
-    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (name) *name = kProfNames[slot];
-    if (total_ms) *total_ms = pr.total_ms[slot];
-    if (launches) *launches = pr.count[slot];
-    pr.total_ms[slot] = 0.0;
-    pr.count[slot] = 0;
+    profile_read_handle(h, slot, name, total_ms, launches);
     SA_API_END
 }
 
@@ -1225,48 +1158,33 @@ int sporco_amd_idctii(int dtype, int32_t H, int32_t W, int64_t P, const void *in
     return spl_dct_api(dtype, H, W, P, in, out, true, on_device);
 }
 
-// ---- BPDN / BPDNJoint / ElasticNet: a handle of its own (csc_impl.h BpdnBase) ------------------------------
-#define SA_BPDN_HANDLE(h)                                                              \
-    SA_REQUIRE((h) != nullptr && (h)->impl, "null bpdn handle");                       \
-    SA_HIP(hipSetDevice((h)->device));
+// ---- BPDN / BPDNJoint / ElasticNet: a side handle (csc_impl.h BpdnBase) ------------------------------
 
 int sporco_amd_bpdn_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_bpdn_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(N >= 1 && M >= 1 && K >= 1, "bpdn: N >= 1, M >= 1, K >= 1");
     SA_REQUIRE(N <= SPORCO_AMD_BPDN_MAX_DIM && M <= SPORCO_AMD_BPDN_MAX_DIM,
                "bpdn: the kernels serve dictionaries of up to 512 rows and 512 columns");
     SA_REQUIRE(K < ((int64_t)1 << 31), "bpdn: fewer than 2^31 signals");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_bpdn> h(new sporco_amd_bpdn);
-    h->device = device;
-    h->impl.reset(make_bpdn(dtype, N, M, K, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_bpdn(dtype, N, M, K, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_bpdn_destroy(sporco_amd_bpdn_t h) {
     SA_API_BEGIN
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
+    destroy_handle(h);
     SA_API_END
 }
 
 int sporco_amd_bpdn_sync(sporco_amd_bpdn_t h) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
-    h->impl->sync();
+    sync_handle(h);
     SA_API_END
 }
 
 int sporco_amd_bpdn_plan(sporco_amd_bpdn_t h, int64_t out[4]) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     h->impl->plan(out);
     SA_API_END
@@ -1274,35 +1192,35 @@ int sporco_amd_bpdn_plan(sporco_amd_bpdn_t h, int64_t out[4]) {
 
 int sporco_amd_bpdn_set_dict(sporco_amd_bpdn_t h, const void *D) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     h->impl->set_dict(D);
     SA_API_END
 }
 
 int sporco_amd_bpdn_set_solve(sporco_amd_bpdn_t h, const void *P) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     h->impl->set_solve(P);
     SA_API_END
 }
 
 int sporco_amd_bpdn_upload(sporco_amd_bpdn_t h, int var, const void *src) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     h->impl->upload(var, src);
     SA_API_END
 }
 
 int sporco_amd_bpdn_download(sporco_amd_bpdn_t h, int var, void *dst) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     h->impl->download(var, dst);
     SA_API_END
 }
 
 int sporco_amd_bpdn_iter(sporco_amd_bpdn_t h, const sporco_amd_bpdn_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
     h->impl->iter(*p, out);
     SA_API_END
@@ -1310,37 +1228,19 @@ int sporco_amd_bpdn_iter(sporco_amd_bpdn_t h, const sporco_amd_bpdn_params *p, d
 
 int sporco_amd_bpdn_profile(sporco_amd_bpdn_t h, int enable) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
-    h->impl->sync();
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (enable)
-        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
-            hipEvent_t e;
-            SA_HIP(hipEventCreate(&e));
-            pr.pool.push_back(e);
-        }
-    pr.on = enable != 0;
+    profile_handle(h, enable);
     SA_API_END
 }
 
 int sporco_amd_bpdn_profile_read(sporco_amd_bpdn_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
-    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (name) *name = kProfNames[slot];
-    if (total_ms) *total_ms = pr.total_ms[slot];
-    if (launches) *launches = pr.count[slot];
-    pr.total_ms[slot] = 0.0;
-    pr.count[slot] = 0;
+    profile_read_handle(h, slot, name, total_ms, launches);
     SA_API_END
 }
 
 int sporco_amd_bpdn_devptr(sporco_amd_bpdn_t h, int var, void **out) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     *out = h->impl->var_ptr(var);
     SA_API_END
@@ -1349,25 +1249,17 @@ int sporco_amd_bpdn_devptr(sporco_amd_bpdn_t h, int var, void **out) {
 // ---- pgm.bpdn BPDN / WeightedBPDN: a bpdn handle with the arrays of the proximal gradient iteration --------------
 int sporco_amd_bpdn_pgm_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_bpdn_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(N >= 1 && M >= 1 && K >= 1, "bpdn: N >= 1, M >= 1, K >= 1");
     SA_REQUIRE(N <= SPORCO_AMD_BPDN_MAX_DIM && M <= SPORCO_AMD_BPDN_MAX_DIM,
                "bpdn: the kernels serve dictionaries of up to 512 rows and 512 columns");
     SA_REQUIRE(K < ((int64_t)1 << 31), "bpdn: fewer than 2^31 signals");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_bpdn> h(new sporco_amd_bpdn);
-    h->device = device;
-    h->impl.reset(make_pgm_bpdn(dtype, N, M, K, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_pgm_bpdn(dtype, N, M, K, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_bpdn_pgm_step(sporco_amd_bpdn_t h, const sporco_amd_bpdn_pgm_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr, "null argument");
     h->impl->pgm_step(*p, out);
     SA_API_END
@@ -1376,61 +1268,46 @@ int sporco_amd_bpdn_pgm_step(sporco_amd_bpdn_t h, const sporco_amd_bpdn_pgm_para
 int sporco_amd_bpdn_pgm_ystep(sporco_amd_bpdn_t h, double beta, double gamma, int use_zz, int advance_y,
                               double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     h->impl->pgm_ystep(beta, gamma, use_zz, advance_y, out);
     SA_API_END
 }
 
 int sporco_amd_bpdn_pgm_copy(sporco_amd_bpdn_t h, int dst, int src) {
     SA_API_BEGIN
-    SA_BPDN_HANDLE(h);
+    check_handle(h);
     h->impl->pgm_copy(dst, src);
     SA_API_END
 }
 
-// ---- CnstrMOD: a handle of its own (csc_impl.h CmodBase) ----------------------------------------------------
-#define SA_CMOD_HANDLE(h)                                                              \
-    SA_REQUIRE((h) != nullptr && (h)->impl, "null cmod handle");                       \
-    SA_HIP(hipSetDevice((h)->device));
+// ---- CnstrMOD: a side handle (csc_impl.h CmodBase) ----------------------------------------------------
 
 int sporco_amd_cmod_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_cmod_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(N >= 1 && M >= 1 && K >= 1, "cmod: N >= 1, M >= 1, K >= 1");
     static_assert(SPORCO_AMD_CMOD_MAX_DIM == kCmodMaxDim, "one limit for the cmod handle");
     SA_REQUIRE(N <= SPORCO_AMD_CMOD_MAX_DIM && M <= SPORCO_AMD_CMOD_MAX_DIM,
                "cmod: the kernels serve dictionaries of up to 512 rows and 512 columns");
     SA_REQUIRE(K < ((int64_t)1 << 31), "cmod: fewer than 2^31 signals");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_cmod> h(new sporco_amd_cmod);
-    h->device = device;
-    h->impl.reset(make_cmod(dtype, N, M, K, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_cmod(dtype, N, M, K, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_cmod_destroy(sporco_amd_cmod_t h) {
     SA_API_BEGIN
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
+    destroy_handle(h);
     SA_API_END
 }
 
 int sporco_amd_cmod_sync(sporco_amd_cmod_t h) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
-    h->impl->sync();
+    sync_handle(h);
     SA_API_END
 }
 
 int sporco_amd_cmod_plan(sporco_amd_cmod_t h, int64_t out[8]) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     h->impl->plan(out);
     SA_API_END
@@ -1438,42 +1315,42 @@ int sporco_amd_cmod_plan(sporco_amd_cmod_t h, int64_t out[8]) {
 
 int sporco_amd_cmod_set_signal(sporco_amd_cmod_t h, const void *S, int on_device) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     h->impl->set_signal(S, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_cmod_set_coef(sporco_amd_cmod_t h, const void *Z, int on_device) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     h->impl->set_coef(Z, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_cmod_set_solve(sporco_amd_cmod_t h, const void *Q) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     h->impl->set_solve(Q);
     SA_API_END
 }
 
 int sporco_amd_cmod_upload(sporco_amd_cmod_t h, int var, const void *src) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     h->impl->upload(var, src);
     SA_API_END
 }
 
 int sporco_amd_cmod_download(sporco_amd_cmod_t h, int var, void *dst) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     h->impl->download(var, dst);
     SA_API_END
 }
 
 int sporco_amd_cmod_iter(sporco_amd_cmod_t h, const sporco_amd_cmod_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
     h->impl->iter(*p, out);
     SA_API_END
@@ -1481,7 +1358,7 @@ int sporco_amd_cmod_iter(sporco_amd_cmod_t h, const sporco_amd_cmod_params *p, d
 
 int sporco_amd_cmod_dfid(sporco_amd_cmod_t h, int var, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     h->impl->dfid(var, out);
     SA_API_END
@@ -1490,32 +1367,24 @@ int sporco_amd_cmod_dfid(sporco_amd_cmod_t h, int var, double out[SPORCO_AMD_OUT
 // ---- pgm.cmod CnstrMOD / WeightedCnstrMOD: a cmod handle with the arrays of the proximal gradient iteration ---------
 int sporco_amd_cmod_pgm_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_cmod_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(N >= 1 && M >= 1 && K >= 1, "cmod: N >= 1, M >= 1, K >= 1");
     SA_REQUIRE(N <= SPORCO_AMD_CMOD_MAX_DIM && M <= SPORCO_AMD_CMOD_MAX_DIM,
                "cmod: the kernels serve dictionaries of up to 512 rows and 512 columns");
     SA_REQUIRE(K < ((int64_t)1 << 31), "cmod: fewer than 2^31 signals");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_cmod> h(new sporco_amd_cmod);
-    h->device = device;
-    h->impl.reset(make_pgm_cmod(dtype, N, M, K, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_pgm_cmod(dtype, N, M, K, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_cmod_pgm_set_weight(sporco_amd_cmod_t h, const void *W, int on_device) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     h->impl->set_weight(W, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_cmod_pgm_step(sporco_amd_cmod_t h, const sporco_amd_cmod_pgm_params *p, double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr, "null argument");
     h->impl->pgm_step(*p, out);
     SA_API_END
@@ -1523,76 +1392,43 @@ int sporco_amd_cmod_pgm_step(sporco_amd_cmod_t h, const sporco_amd_cmod_pgm_para
 
 int sporco_amd_cmod_profile(sporco_amd_cmod_t h, int enable) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
-    h->impl->sync();
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (enable)
-        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
-            hipEvent_t e;
-            SA_HIP(hipEventCreate(&e));
-            pr.pool.push_back(e);
-        }
-    pr.on = enable != 0;
+    profile_handle(h, enable);
     SA_API_END
 }
 
 int sporco_amd_cmod_profile_read(sporco_amd_cmod_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
     SA_API_BEGIN
-    SA_CMOD_HANDLE(h);
-    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (name) *name = kProfNames[slot];
-    if (total_ms) *total_ms = pr.total_ms[slot];
-    if (launches) *launches = pr.count[slot];
-    pr.total_ms[slot] = 0.0;
-    pr.count[slot] = 0;
+    profile_read_handle(h, slot, name, total_ms, launches);
     SA_API_END
 }
 
-// ---- RobustPCA / prox_nuclear: a handle of its own (csc_impl.h RpcaBase) --------------------------------------
-#define SA_RPCA_HANDLE(h)                                                              \
-    SA_REQUIRE((h) != nullptr && (h)->impl, "null rpca handle");                       \
-    SA_HIP(hipSetDevice((h)->device));
+// ---- RobustPCA / prox_nuclear: a side handle (csc_impl.h RpcaBase) --------------------------------------
 
 int sporco_amd_rpca_create(int dtype, int32_t R, int32_t C, int device, void *stream, sporco_amd_rpca_t *out) {
     SA_API_BEGIN
-    SA_REQUIRE(out != nullptr, "null argument");
     SA_REQUIRE(R >= 1 && C >= 1, "rpca: R >= 1, C >= 1");
     static_assert(SPORCO_AMD_RPCA_MAX_DIM == kRpcaMaxDim, "one limit for the rpca handle");
     SA_REQUIRE((R < C ? R : C) <= SPORCO_AMD_RPCA_MAX_DIM, "rpca: the kernels serve arrays whose short side is at most 512");
     SA_REQUIRE((int64_t)R * C < ((int64_t)1 << 31), "rpca: fewer than 2^31 elements");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        throw Error(SPORCO_AMD_EHIP, "no HIP device visible: libsporco_amd needs an AMD GPU");
-    SA_REQUIRE(device >= 0 && device < n, "device index out of range");
-    std::unique_ptr<sporco_amd_rpca> h(new sporco_amd_rpca);
-    h->device = device;
-    h->impl.reset(make_rpca(dtype, R, C, device, stream));
-    *out = h.release();
+    create_handle(device, out, [&] { return make_rpca(dtype, R, C, device, stream); });
     SA_API_END
 }
 
 int sporco_amd_rpca_destroy(sporco_amd_rpca_t h) {
     SA_API_BEGIN
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
+    destroy_handle(h);
     SA_API_END
 }
 
 int sporco_amd_rpca_sync(sporco_amd_rpca_t h) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
-    h->impl->sync();
+    sync_handle(h);
     SA_API_END
 }
 
 int sporco_amd_rpca_plan(sporco_amd_rpca_t h, int64_t out[10]) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     h->impl->plan(out);
     SA_API_END
@@ -1600,28 +1436,28 @@ int sporco_amd_rpca_plan(sporco_amd_rpca_t h, int64_t out[10]) {
 
 int sporco_amd_rpca_set_signal(sporco_amd_rpca_t h, const void *S, int on_device) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     h->impl->set_signal(S, on_device != 0);
     SA_API_END
 }
 
 int sporco_amd_rpca_upload(sporco_amd_rpca_t h, int var, const void *src) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     h->impl->upload(var, src);
     SA_API_END
 }
 
 int sporco_amd_rpca_download(sporco_amd_rpca_t h, int var, void *dst) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     h->impl->download(var, dst);
     SA_API_END
 }
 
 int sporco_amd_rpca_devptr(sporco_amd_rpca_t h, int var, void **out) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(out != nullptr, "null argument");
     *out = h->impl->var_ptr(var);
     SA_API_END
@@ -1629,7 +1465,7 @@ int sporco_amd_rpca_devptr(sporco_amd_rpca_t h, int var, void **out) {
 
 int sporco_amd_rpca_gram(sporco_amd_rpca_t h, int mode, double u_scale, double *G) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     h->impl->gram(mode, u_scale, G);
     SA_API_END
 }
@@ -1637,7 +1473,7 @@ int sporco_amd_rpca_gram(sporco_amd_rpca_t h, int mode, double u_scale, double *
 int sporco_amd_rpca_iter(sporco_amd_rpca_t h, const sporco_amd_rpca_params *p, const double *T,
                          double out[SPORCO_AMD_OUT_COUNT]) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     SA_REQUIRE(p != nullptr && out != nullptr, "null argument");
     h->impl->iter(*p, T, out);
     SA_API_END
@@ -1645,38 +1481,20 @@ int sporco_amd_rpca_iter(sporco_amd_rpca_t h, const sporco_amd_rpca_params *p, c
 
 int sporco_amd_rpca_apply(sporco_amd_rpca_t h, const double *T) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
+    check_handle(h);
     h->impl->apply(T);
     SA_API_END
 }
 
 int sporco_amd_rpca_profile(sporco_amd_rpca_t h, int enable) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
-    h->impl->sync();
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (enable)
-        while (pr.pool.size() < 512) {      // (up front: hipEventCreate inside a timed region distorts it)
-            hipEvent_t e;
-            SA_HIP(hipEventCreate(&e));
-            pr.pool.push_back(e);
-        }
-    pr.on = enable != 0;
+    profile_handle(h, enable);
     SA_API_END
 }
 
 int sporco_amd_rpca_profile_read(sporco_amd_rpca_t h, int slot, const char **name, double *total_ms, int64_t *launches) {
     SA_API_BEGIN
-    SA_RPCA_HANDLE(h);
-    SA_REQUIRE(slot >= 0 && slot < PS_COUNT, "timing slot out of range");
-    Profiler &pr = h->impl->prof;
-    pr.drain();
-    if (name) *name = kProfNames[slot];
-    if (total_ms) *total_ms = pr.total_ms[slot];
-    if (launches) *launches = pr.count[slot];
-    pr.total_ms[slot] = 0.0;
-    pr.count[slot] = 0;
+    profile_read_handle(h, slot, name, total_ms, launches);
     SA_API_END
 }
 

@@ -1,6 +1,7 @@
 // csc_impl.h -- what the translation units behind the C ABI share: transfer counting, the
 // per-kernel event profiler, the type-erased solver interface (CscBase) that the extern "C"
-// glue (csc_abi.hip) talks to, and the error-to-return-code macros.  The solver itself
+// glue (csc_abi.hip) talks to, the base of the side handles (SideBase) with their type-erased
+// interfaces, and the error-to-return-code macros.  The solver itself
 // (template Csc<T>, csc_api.hip + api_*.inc) is only visible through make_csc().
 #pragma once
 #include "../../include/sporco_amd.h"
@@ -349,11 +350,70 @@ static bool var_is_valid(int var) {
            (var >= SPORCO_AMD_VAR_DX && var < SPORCO_AMD_VAR_COUNT);
 }
 
+// What every side handle (TVL2Denoise ... RobustPCA: a problem of its own beside the convolutional solver) has: the
+// device and stream, the profiler, the sums with their pinned read-back, and the list of the device buffers it keeps
+// for its lifetime.  Base destructors run when a derived constructor throws, so a handle that allocates through
+// dev_alloc leaves nothing behind whichever allocation fails.
+struct SideBase {
+    const int device;
+    hipStream_t st = nullptr;
+    bool own_stream = false;
+    Profiler prof;
+    double *out_dev = nullptr, *out_pinned = nullptr;
+    FftPlan planH, planW;           // of the handles that transform (Tvdc, Spl); their tables go with the handle
+    std::vector<void *> owned;
+
+    SideBase(int device_, void *stream) : device(device_) {
+        SA_HIP(hipSetDevice(device));
+        if (stream) {
+            st = (hipStream_t)stream;
+        } else {
+            SA_HIP(hipStreamCreate(&st));
+            own_stream = true;
+        }
+        prof.st = st;
+        try {
+            out_dev = dev_alloc<double>(kOutSlots, true);
+            SA_HIP(hipHostMalloc((void **)&out_pinned, sizeof(double) * kOutSlots, 0));
+        } catch (...) {
+            release();      // (the one constructor that has to: no base below it)
+            throw;
+        }
+    }
+    SideBase(const SideBase &) = delete;
+    SideBase &operator=(const SideBase &) = delete;
+    virtual ~SideBase() { release(); }
+
+    // count elements of U for the handle's lifetime, zeroed on its stream if asked
+    template <class U> U *dev_alloc(size_t count, bool zero) {
+        owned.push_back(nullptr);      // (first: a pointer that hipMalloc has returned is on the list)
+        SA_HIP(hipMalloc(&owned.back(), sizeof(U) * count));
+        if (zero) SA_HIP(hipMemsetAsync(owned.back(), 0, sizeof(U) * count, st));
+        return (U *)owned.back();
+    }
+    void sync() { SA_HIP(hipStreamSynchronize(st)); }
+    void read_out(double *out_host) {
+        SA_HIP(hipMemcpyAsync(out_pinned, out_dev, sizeof(double) * kOutSlots, hipMemcpyDeviceToHost, st));
+        sync();
+        std::memcpy(out_host, out_pinned, sizeof(double) * kOutSlots);
+    }
+
+private:
+    void release() {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(st);
+        for (void *p : owned) (void)hipFree(p);
+        if (out_pinned) (void)hipHostFree(out_pinned);
+        planH.destroy();
+        planW.destroy();
+        if (own_stream) (void)hipStreamDestroy(st);
+    }
+};
+
 // The handle of TVL2Denoise and, in its l1 mode, TVL1Denoise (api_tvd.inc): the arrays of one (H, W, P)
 // problem and a stream.
-struct TvdBase {
-    virtual ~TvdBase() {}
-    virtual void sync() = 0;
+struct TvdBase : SideBase {
+    using SideBase::SideBase;
     virtual void plan(int64_t out[6]) = 0;
     virtual void upload(int var, const void *src, bool on_device) = 0;
     virtual void download(int var, void *dst, bool on_device) = 0;
@@ -361,15 +421,13 @@ struct TvdBase {
     virtual void gsres(const sporco_amd_tvd_params &p, double *out_host) = 0;
     virtual void ystep(const sporco_amd_tvd_params &p, double *out_host) = 0;
     virtual void adjoint() = 0;
-    Profiler prof;
 };
 TvdBase *make_tvd(int dtype, int H, int W, int64_t P, int C, bool vector_tv, bool l1, int device, void *stream);
 
 // The handle of TVL2Deconv and, in its l1 mode, TVL1Deconv (api_tvdc.inc): the arrays and spectra of one
 // (H, W, P) problem, the transform plans of H and W and a stream.
-struct TvdcBase {
-    virtual ~TvdcBase() {}
-    virtual void sync() = 0;
+struct TvdcBase : SideBase {
+    using SideBase::SideBase;
     virtual void plan(int64_t out[8]) = 0;
     virtual void upload(int var, const void *src, bool on_device) = 0;
     virtual void download(int var, void *dst, bool on_device) = 0;
@@ -377,22 +435,19 @@ struct TvdcBase {
     virtual void xstep(const sporco_amd_tvdc_params &p) = 0;
     virtual void ystep(const sporco_amd_tvdc_params &p, double *out_host) = 0;
     virtual void adjoint() = 0;
-    Profiler prof;
 };
 TvdcBase *make_tvdc(int dtype, int H, int W, int64_t P, int C, bool vector_tv, bool l1, int64_t PA, int device,
                     void *stream);
 
 // The handle of SplineL1 (api_spline.inc): the arrays of one (H, W, P) problem, the work spectrum, the DCT's
 // tables, the transform plans of H and W and a stream.
-struct SplBase {
-    virtual ~SplBase() {}
-    virtual void sync() = 0;
+struct SplBase : SideBase {
+    using SideBase::SideBase;
     virtual void plan(int64_t out[4]) = 0;
     virtual void upload(int var, const void *src, bool on_device) = 0;
     virtual void download(int var, void *dst, bool on_device) = 0;
     virtual void xstep(const sporco_amd_spl_params &p) = 0;
     virtual void ystep(const sporco_amd_spl_params &p, double *out_host) = 0;
-    Profiler prof;
 };
 SplBase *make_spl(int dtype, int H, int W, int64_t P, int device, void *stream);
 // the stateless orthonormal DCT-II (inverse: its inverse) over axes (0, 1) of an (H, W, P) array
@@ -400,9 +455,8 @@ void spl_dct_dispatch(int dtype, int H, int W, int64_t P, const void *in, void *
 
 // The handle of BPDN, BPDNJoint and ElasticNet (api_bpdn.inc): the arrays of one (N, M, K) problem, the dictionary and
 // the solve matrix in the order the product routine reads them, and a stream.
-struct BpdnBase {
-    virtual ~BpdnBase() {}
-    virtual void sync() = 0;
+struct BpdnBase : SideBase {
+    using SideBase::SideBase;
     virtual void plan(int64_t out[4]) = 0;
     virtual void set_dict(const void *D) = 0;
     virtual void set_solve(const void *P) = 0;
@@ -417,16 +471,14 @@ struct BpdnBase {
     [[noreturn]] static void no_pgm() {
         throw Error(SPORCO_AMD_EINVAL, "bpdn: the handle was not made by sporco_amd_bpdn_pgm_create");
     }
-    Profiler prof;
 };
 BpdnBase *make_bpdn(int dtype, int N, int M, int64_t K, int device, void *stream);
 BpdnBase *make_pgm_bpdn(int dtype, int N, int M, int64_t K, int device, void *stream);
 
 // The handle of CnstrMOD (api_cmod.inc): the dictionary variables of one (N, M, K) problem in the order the product
 // routine reads them, the Gram matrices of the coefficients, its own or a borrowed Z and S, and a stream.
-struct CmodBase {
-    virtual ~CmodBase() {}
-    virtual void sync() = 0;
+struct CmodBase : SideBase {
+    using SideBase::SideBase;
     virtual void plan(int64_t out[8]) = 0;
     virtual void set_signal(const void *S, bool on_device) = 0;
     virtual void set_coef(const void *Z, bool on_device) = 0;
@@ -441,16 +493,14 @@ struct CmodBase {
     [[noreturn]] static void no_pgm() {
         throw Error(SPORCO_AMD_EINVAL, "cmod: the handle was not made by sporco_amd_cmod_pgm_create");
     }
-    Profiler prof;
 };
 CmodBase *make_cmod(int dtype, int N, int M, int64_t K, int device, void *stream);
 CmodBase *make_pgm_cmod(int dtype, int N, int M, int64_t K, int device, void *stream);
 
 // The handle of RobustPCA and of the stateless prox_nuclear / norm_nuclear (api_rpca.inc): X, Y, U of one (R, C)
 // problem as NumPy has them, its own or a borrowed S, the Gram matrix and its slab partials, T, and a stream.
-struct RpcaBase {
-    virtual ~RpcaBase() {}
-    virtual void sync() = 0;
+struct RpcaBase : SideBase {
+    using SideBase::SideBase;
     virtual void plan(int64_t out[10]) = 0;
     virtual void set_signal(const void *S, bool on_device) = 0;
     virtual void upload(int var, const void *src) = 0;
@@ -459,7 +509,6 @@ struct RpcaBase {
     virtual void gram(int mode, double u_scale, double *G_host) = 0;
     virtual void iter(const sporco_amd_rpca_params &p, const double *T_host, double *out_host) = 0;
     virtual void apply(const double *T_host) = 0;
-    Profiler prof;
 };
 RpcaBase *make_rpca(int dtype, int R, int C, int device, void *stream);
 
@@ -480,35 +529,17 @@ struct sporco_amd_csc {
     }
 };
 
-struct sporco_amd_tvd {
-    std::unique_ptr<sporco_amd::TvdBase> impl;
+// the six side handles: the implementation and the device that the glue selects before it calls
+template <class B> struct SideHandle {
+    std::unique_ptr<B> impl;
     int device;
 };
-
-struct sporco_amd_tvdc {
-    std::unique_ptr<sporco_amd::TvdcBase> impl;
-    int device;
-};
-
-struct sporco_amd_spl {
-    std::unique_ptr<sporco_amd::SplBase> impl;
-    int device;
-};
-
-struct sporco_amd_bpdn {
-    std::unique_ptr<sporco_amd::BpdnBase> impl;
-    int device;
-};
-
-struct sporco_amd_cmod {
-    std::unique_ptr<sporco_amd::CmodBase> impl;
-    int device;
-};
-
-struct sporco_amd_rpca {
-    std::unique_ptr<sporco_amd::RpcaBase> impl;
-    int device;
-};
+struct sporco_amd_tvd : SideHandle<sporco_amd::TvdBase> {};
+struct sporco_amd_tvdc : SideHandle<sporco_amd::TvdcBase> {};
+struct sporco_amd_spl : SideHandle<sporco_amd::SplBase> {};
+struct sporco_amd_bpdn : SideHandle<sporco_amd::BpdnBase> {};
+struct sporco_amd_cmod : SideHandle<sporco_amd::CmodBase> {};
+struct sporco_amd_rpca : SideHandle<sporco_amd::RpcaBase> {};
 
 #define SA_API_BEGIN try {
 #define SA_API_END                                                                     \
@@ -528,7 +559,7 @@ struct sporco_amd_rpca {
     return SPORCO_AMD_OK;
 
 #define SA_HANDLE_ANY(h)                                                               \
-    SA_REQUIRE((h) != nullptr && (h)->impl, "null solver handle");                     \
+    SA_REQUIRE((h) != nullptr && (h)->impl, "null handle");                            \
     SA_HIP(hipSetDevice((h)->device));
 // (every entry point that has not been taught the third transform axis refuses a volume handle)
 #define SA_HANDLE(h)                                                                   \
