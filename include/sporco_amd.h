@@ -1277,7 +1277,10 @@ typedef struct {
     int32_t want_x;           /* store X (always stored with joint or lin_solve_check)                      */
     int32_t joint;            /* BPDNJoint: the l2,1 term with weight mu                                    */
     int32_t lin_solve_check;  /* also form OUT_XRRS_*                                                       */
-    int32_t reserved[2];
+    int32_t proj_l1;          /* BPDNProjL1 (bpdn.py:750-914): the y step projects every column of AX + U onto
+                                 the l1 ball of radius gamma, and `lmbda` carries gamma (>= 0); wl1, mu and a
+                                 weight array are not read; not with joint                                  */
+    int32_t reserved;
 } sporco_amd_bpdn_params;
 int sporco_amd_bpdn_create(int dtype, int32_t N, int32_t M, int64_t K, int device, void *stream, sporco_amd_bpdn_t *out);
 int sporco_amd_bpdn_destroy(sporco_amd_bpdn_t h);
@@ -1294,8 +1297,17 @@ int sporco_amd_bpdn_download(sporco_amd_bpdn_t h, int var, void *dst);
 /* One iteration: x step, relax_AX, y step, u step, one reduction, one host read.  out: OUT_R2 = ||X - Y||^2,
  * OUT_AX2 = ||X||^2, OUT_Y2, OUT_S2 = ||Y - Yprev||^2 (rho applied by the host), OUT_U2, OUT_DFID =
  * ||D g - S||^2 (the host halves it), OUT_L1 = sum |wl1 g|, joint: OUT_L21 = sum_m ||g_m||, with
- * lin_solve_check: OUT_XRRS_*.  U is stored with u_scale applied: the pending factor is 1 afterwards. */
+ * lin_solve_check: OUT_XRRS_*.  U is stored with u_scale applied: the pending factor is 1 afterwards.
+ * proj_l1: Y' = proj_l1(AX + U, gamma) per column [max(., 0)], OUT_L1 is not formed, and
+ * SPORCO_AMD_OUT_BPDN_CNSTR = sum (proj_l1(g, gamma) - g)^2 over the columns of g = Y' (geval_y off: X), the
+ * square of the reference's Cnstr (bpdn.py:906-914). */
+#define SPORCO_AMD_OUT_BPDN_CNSTR SPORCO_AMD_OUT_CNSTR
 int sporco_amd_bpdn_iter(sporco_amd_bpdn_t h, const sporco_amd_bpdn_params *p, double out[SPORCO_AMD_OUT_COUNT]);
+/* prox.proj_l1(v, gamma, axis=0) of a host (M, K) array, row-major, M <= 512, gamma >= 0: one l1 ball per column,
+ * by the column search of the proj_l1 mode above behind a kernel that loads tiles and stores the result
+ * (csrc/csc_bpdn.h).  The columns of a workgroup's block are those of sporco_amd_bpdn_plan for (N = 1, M).  Stateless
+ * as the primitives above: current device, null stream, synchronises. */
+int sporco_amd_proj_l1_cols(int dtype, int32_t M, int64_t K, const void *v, double gamma, void *out);
 /* Per-kernel event timing of the handle's launches, as sporco_amd_csc_profile / _profile_read. */
 int sporco_amd_bpdn_profile(sporco_amd_bpdn_t h, int enable);
 int sporco_amd_bpdn_profile_read(sporco_amd_bpdn_t h, int slot, const char **name, double *total_ms,

@@ -103,7 +103,7 @@ EXPORTS = (
     'sporco_amd_csc_set_comm',
     'sporco_amd_rfftn2', 'sporco_amd_irfftn2', 'sporco_amd_solvedbi_sm',
     'sporco_amd_inner', 'sporco_amd_prox_l1', 'sporco_amd_prox_l1w', 'sporco_amd_prox_sl1l2',
-    'sporco_amd_proj_l2', 'sporco_amd_proj_l1', 'sporco_amd_rfl2norm2',
+    'sporco_amd_proj_l2', 'sporco_amd_proj_l1', 'sporco_amd_proj_l1_cols', 'sporco_amd_rfl2norm2',
     'sporco_amd_dev_mul',
     'sporco_amd_tvd_create', 'sporco_amd_tvl1_create', 'sporco_amd_tvd_destroy', 'sporco_amd_tvd_sync', 'sporco_amd_tvd_plan',
     'sporco_amd_tvd_upload', 'sporco_amd_tvd_download', 'sporco_amd_tvd_sweeps', 'sporco_amd_tvd_gsres',
@@ -219,15 +219,18 @@ SPL_S, SPL_X, SPL_Y, SPL_U, SPL_WDF = range(5)
 
 
 class BpdnParams(ctypes.Structure):
-    """sporco_amd_bpdn_params: scalars of one BPDN / BPDNJoint / ElasticNet iteration."""
+    """sporco_amd_bpdn_params: scalars of one BPDN / BPDNJoint / ElasticNet / BPDNProjL1 iteration.  ``proj_l1``: the
+    y step projects every column onto the l1 ball, ``lmbda`` carries its radius gamma and the sums come back with
+    ``OUT_BPDN_CNSTR``."""
     _fields_ = [('rho', ctypes.c_double), ('lmbda', ctypes.c_double), ('mu', ctypes.c_double),
                 ('rlx', ctypes.c_double), ('u_scale', ctypes.c_double), ('wl1', ctypes.c_double),
                 ('c', ctypes.c_double),
                 ('nonneg', ctypes.c_int32), ('feval_x', ctypes.c_int32), ('geval_y', ctypes.c_int32),
                 ('want_x', ctypes.c_int32), ('joint', ctypes.c_int32), ('lin_solve_check', ctypes.c_int32),
-                ('reserved', ctypes.c_int32 * 2)]
+                ('proj_l1', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+OUT_BPDN_CNSTR = OUT_CNSTR     # bpdn_iter with proj_l1: sum (proj_l1(g, gamma) - g)^2
 BPDN_S, BPDN_X, BPDN_Y, BPDN_U, BPDN_WL1, BPDN_DTS = range(6)
 BPDN_MAX_DIM = 512
 
@@ -491,6 +494,7 @@ def load(path=None):
         'sporco_amd_prox_sl1l2': [ctypes.c_int, i64, i32, i64, vp, dbl, dbl, vp],
         'sporco_amd_proj_l2': [ctypes.c_int, i64, i64, i64, vp, dbl, vp],
         'sporco_amd_proj_l1': [ctypes.c_int, i64, i64, i64, vp, dbl, vp],
+        'sporco_amd_proj_l1_cols': [ctypes.c_int, i32, i64, vp, dbl, vp],
         'sporco_amd_rfl2norm2': [ctypes.c_int, i32, i32, i64, vp, dptr],
         'sporco_amd_dev_mul': [ctypes.c_int, i64, vp, vp, vp],
         'sporco_amd_tvd_create': [ctypes.c_int, i32, i32, i64, i32, i32, ctypes.c_int, vp, ctypes.POINTER(vp)],
@@ -1795,4 +1799,17 @@ def dct2(a, out=None, inverse=False):
     if out is None or tuple(out.shape) != tuple(a.shape) or out.dtype != a.dtype or out.ptr == a.ptr:
         raise ValueError("a device array is transformed into another of the same shape and dtype")
     check(fn(dtype_code(a.dtype), H, W, P, ctypes.c_void_p(a.ptr), ctypes.c_void_p(out.ptr), 1))
+    return out
+
+
+def proj_l1_cols(v, gamma):
+    """``proj_l1(v, gamma, axis=0)`` of a host ``(M, K)`` array, ``M <= 512``: one l1 ball per column, by the column
+    search of the bpdn handle's projection mode (sporco_amd_proj_l1_cols).  What the tests reach that routine with."""
+    v = np.asarray(v)
+    if v.ndim != 2 or v.dtype not in (np.float32, np.float64):
+        raise ValueError("proj_l1_cols takes a float32 or float64 array of shape (M, K)")
+    v = _carr(v, v.dtype)
+    out = np.full(v.shape, np.nan, dtype=v.dtype)
+    check(lib().sporco_amd_proj_l1_cols(dtype_code(v.dtype), int(v.shape[0]), int(v.shape[1]), _ptr(v), float(gamma),
+                                        _ptr(out)))
     return out

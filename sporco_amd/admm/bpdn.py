@@ -1,6 +1,7 @@
 """Dense (patch-based) sparse coding on the device, with the interface of the reference's ``sporco.admm.bpdn``
-(sporco/admm/bpdn.py:24-748): :class:`BPDN`, :class:`BPDNJoint` and :class:`ElasticNet`, the three classes of
-:class:`GenericBPDN` that share one x step.
+(sporco/admm/bpdn.py:24-914): :class:`BPDN`, :class:`BPDNJoint`, :class:`ElasticNet` and :class:`BPDNProjL1`, the
+classes of :class:`GenericBPDN` that share one x step.  :class:`BPDNProjL1` replaces the l1 penalty by the constraint
+``||x||_1 <= gamma`` per signal: its y step projects every column onto the l1 ball inside the same launch.
 
 The dictionary ``D`` is ``(N, M)``, the signals ``S`` are ``(N, K)``, the coefficients ``(M, K)``.  The x step is
 ``X = P (D^T S + rho (Y - U))`` with ``P = (D^T D + c I)^-1``, ``c = rho`` (``ElasticNet``: ``mu + rho``).  The host
@@ -14,7 +15,7 @@ a scalar or an array that broadcasts to ``(M, K)``, ``NonNegCoef``, ``AuxVarObj`
 ``Y0`` / ``U0``, ``AutoRho``, ``setdict``.
 
 Refused: complex or non-floating ``D`` / ``S`` and :class:`sporco_amd.device.DeviceArray` inputs (``TypeError``),
-``M`` or ``N`` above 512 and shape mismatches (``ValueError``), ``reducer=`` and pickling
+``M`` or ``N`` above 512, shape mismatches and a negative ``gamma`` (``ValueError``), ``reducer=`` and pickling
 (``NotImplementedError``).  The reference's attributes ``lu`` and ``piv`` do not exist.  There is no CPU path.
 """
 
@@ -27,7 +28,7 @@ from .. import _lib
 from ..device import is_device_array
 from . import admm
 
-__all__ = ['GenericBPDN', 'BPDN', 'BPDNJoint', 'ElasticNet']
+__all__ = ['GenericBPDN', 'BPDN', 'BPDNJoint', 'ElasticNet', 'BPDNProjL1']
 
 
 def solve_matrix(D, c):
@@ -264,7 +265,7 @@ class GenericBPDN(admm.ADMMEqual):
     def _params(self):
         p = _lib.BpdnParams()
         p.rho = float(self.rho)
-        p.lmbda = float(self.lmbda)
+        p.lmbda = float(getattr(self, 'lmbda', 0.0))
         p.mu = float(getattr(self, 'mu', 0.0))
         p.rlx = float(self.rlx)
         p.u_scale = float(self._u_scale)
@@ -456,3 +457,53 @@ class ElasticNet(BPDN):
         rl1 = self._sums[_lib.OUT_L1]
         rl2 = 0.5 * self._gvar_norm2()
         return (float(self.lmbda) * rl1 + float(self.mu) * rl2, rl1, rl2)
+
+
+class BPDNProjL1(GenericBPDN):
+    r"""ADMM algorithm for  minimise (1/2) ||D x - s||^2  such that  ||x||_1 <= gamma  per signal (bpdn.py:750-914).
+    The y step is ``proj_l1(AX + U, gamma, axis=0)``, found per column inside the iteration's launch
+    (csrc/csc_bpdn.h, projection mode).
+
+    ``IterationStats``: ``Iter, ObjFun, Cnstr, PrimalRsdl, DualRsdl, EpsPrimal, EpsDual, Rho, XSlvRelRes, Time``;
+    ``ObjFun`` is the data fidelity alone, ``Cnstr`` is ``||proj_l1(g, gamma) - g||`` with ``g = Y`` (``AuxVarObj``
+    off: ``X``).
+    """
+
+    class Options(GenericBPDN.Options):
+        """The options of :class:`GenericBPDN.Options` with ``AutoRho.RsdlTarget`` 1.0 (bpdn.py:816-837)."""
+
+        defaults = copy.deepcopy(GenericBPDN.Options.defaults)
+        defaults['AutoRho'].update({'RsdlTarget': 1.0})
+
+        def __init__(self, opt=None):
+            GenericBPDN.Options.__init__(self, {} if opt is None else opt)
+
+    itstat_fields_objfn = ('ObjFun', 'Cnstr')
+    hdrtxt_objfn = ('Fnc', 'Cnstr')
+    hdrval_objfun = {'Fnc': 'ObjFun', 'Cnstr': 'Cnstr'}
+
+    def __init__(self, D, S, gamma, opt=None, **backend):
+        if opt is None:
+            opt = BPDNProjL1.Options()
+        D, S = self._check_inputs(D, S, backend)
+        self.set_dtype(opt, S.dtype)
+        if self.dtype not in (np.float32, np.float64):
+            raise TypeError("sporco_amd works in float32 or float64, not %s" % self.dtype)
+        if not float(gamma) >= 0.0:
+            raise ValueError("gamma must not be negative")
+        self.gamma = self.dtype.type(gamma)
+        super(BPDNProjL1, self).__init__(D, S, opt, **backend)
+
+    def uinit(self, ushape):
+        """bpdn.py:881-891: zero, with a ``Y0`` too."""
+        return np.zeros(ushape, dtype=self.dtype)
+
+    def _params(self):
+        p = super(BPDNProjL1, self)._params()
+        p.lmbda = float(self.gamma)      # (the radius travels in the lmbda field)
+        p.proj_l1 = 1
+        return p
+
+    def eval_objfn(self):
+        """bpdn.py:906-914: the data fidelity and the distance of the g variable from the l1 balls."""
+        return (self.obfn_dfd(), float(np.sqrt(self._sums[_lib.OUT_BPDN_CNSTR])))

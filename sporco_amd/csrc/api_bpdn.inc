@@ -1,4 +1,4 @@
-// api_bpdn.inc -- the handle of BPDN / BPDNJoint / ElasticNet (sporco/admm/bpdn.py:24-748); kernels: csc_bpdn.h.
+// api_bpdn.inc -- the handle of BPDN / BPDNJoint / ElasticNet / BPDNProjL1 (sporco/admm/bpdn.py:24-914); kernels: csc_bpdn.h.
 // It is included by csc_api.hip at namespace scope; the stream, the sums, the profiler and the ownership of every
 // buffer are SideBase's (csc_impl.h).  S is (N, K); X, Y, U, D^T S, the weight,
 // Z and the saved right-hand side are (M, K), all row-major as NumPy has them.  The dictionary and the solve
@@ -148,6 +148,12 @@ template <typename T> struct Bpdn : BpdnBase {
         a.feval_x = p.feval_x;
         a.geval_y = p.geval_y;
         a.joint = p.joint;
+        a.proj_l1 = p.proj_l1;
+        if (p.proj_l1) {
+            SA_REQUIRE(!p.joint && p.lmbda >= 0.0, "bpdn: proj_l1 takes gamma >= 0 in lmbda and no joint term");
+            a.gamma = p.lmbda;
+            a.lr = T(0);
+        }
         a.want_x = (p.want_x || p.lin_solve_check || p.joint) ? 1 : 0;
         if (p.lin_solve_check) {
             need(&bsave);
@@ -193,14 +199,15 @@ template <typename T> struct Bpdn : BpdnBase {
             lsc_vals = kBpdnLscSums;
         }
         // (bpdn_sums order; OUT_AX2 = || X ||^2: the residuals are those of ADMMEqual, on the unrelaxed X)
-        const int slots[7] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_AX2, SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_S2,
-                              SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_L1};
+        // projection mode: the eighth sum, BPDN_CNSTR
+        const int slots[8] = {SPORCO_AMD_OUT_R2, SPORCO_AMD_OUT_AX2, SPORCO_AMD_OUT_Y2, SPORCO_AMD_OUT_S2,
+                              SPORCO_AMD_OUT_U2, SPORCO_AMD_OUT_DFID, SPORCO_AMD_OUT_L1, SPORCO_AMD_OUT_BPDN_CNSTR};
         const int slots_l[3] = {SPORCO_AMD_OUT_XRRS_D2, SPORCO_AMD_OUT_XRRS_AX2, SPORCO_AMD_OUT_XRRS_B2};
-        const double ones[7] = {1, 1, 1, 1, 1, 1, 1};
+        const double ones[8] = {1, 1, 1, 1, 1, 1, 1, 1};
         {
             ProfScope ps(prof, PS_FINALIZE);
-            launch_finalize2(st, part, nb, kBpdnSums, 7, slots, ones, part_lsc ? part_lsc : part, nb, kBpdnLscSums, lsc_vals,
-                             slots_l, ones, out_dev);
+            launch_finalize2(st, part, nb, kBpdnSums, p.proj_l1 ? 8 : 7, slots, ones, part_lsc ? part_lsc : part, nb,
+                             kBpdnLscSums, lsc_vals, slots_l, ones, out_dev);
         }
         read_out(out_host);
     }

@@ -24,6 +24,19 @@
 // bpdn_joint_apply does the rest of the iteration and leaves row sums of Y'^2; bpdn_joint_rows reduces those to
 // sum_m || Y'_m ||.  Sums are per-workgroup partials in double, reduced by launch_finalize in a fixed order: no
 // floating-point atomics, two runs agree bit for bit.
+//
+// projection mode (BpdnArgs::proj_l1, BPDNProjL1, sporco/admm/bpdn.py:750-914): the y step is the projection of every
+// column of V = AX + U onto the l1 ball of radius gamma, Y' = soft(V, tau_j) with tau_j >= 0 such that
+// sum_i max(|v_ij| - tau_j, 0) = gamma (0 where the column lies inside).  V takes the place of B in LDS and the
+// thresholds are found there, by the column search of csc_bpdn.hip (bp_col_tau): 256 / KB lanes of one wave own a
+// column, sum |v| and count the entries above the current threshold in double, reduce both by xor shuffles in a fixed
+// order, and set tau = (sum - gamma) / count until the count comes back unchanged (Michelot's iteration: the active
+// set only shrinks, so M + 1 passes bound it; the loop is capped there, and it ends at once on a count of zero,
+// which is all a NaN or an infinite threshold leaves).  A wave goes on while any of its columns is unsettled; no
+// barrier of the workgroup lies inside the loop.  A second search on the tile of g = Y' (gEvalY off: X) gives
+// sum (proj_l1(g) - g)^2, the square of the reference's Cnstr, in the sum slot BPDN_CNSTR.  The thresholds of a block
+// pass through the 32 doubles of the reduction scratch, which nothing else uses before the last block is done:
+// the mode needs no LDS beyond bpdn_lds_bytes.  bpdn_proj_cols runs the same search on a plain (M, K) array.
 #pragma once
 
 #include "csc_kernels.h"
@@ -35,6 +48,7 @@ constexpr int kBpdnMaxBlocks = 1024; // the most workgroups of a kernel here; a 
 constexpr int kBpdnSums = 8;         // doubles a workgroup of bpdn_iter / bpdn_joint_apply leaves (bpdn_sums)
 constexpr int kBpdnLscSums = 3;      // ... and of bpdn_lsc
 enum bpdn_sums { BPDN_R2 = 0, BPDN_X2, BPDN_Y2, BPDN_S2, BPDN_U2, BPDN_DFID, BPDN_L1, BPDN_SPARE };
+constexpr int BPDN_CNSTR = BPDN_SPARE;   // projection mode: sum (proj_l1(g) - g)^2
 enum bpdn_form { BPDN_FORM_PLAIN = 0, BPDN_FORM_MFMA = 1 };
 
 inline int bpdn_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -66,6 +80,8 @@ template <typename T> struct BpdnArgs {
     T wl1_s = T(1);
     T rho = T(1), lr = T(0), rlx = T(1), u_scale = T(1), c = T(1);     // lr = lmbda / rho, c = rho [+ mu]
     int nonneg = 0, feval_x = 0, geval_y = 1, want_x = 1, joint = 0, form = BPDN_FORM_PLAIN;
+    int proj_l1 = 0;             // the y step projects onto l1 balls of radius gamma (lr, wl1 and wl1_s are not read)
+    double gamma = 0.0;
     int M = 1, N = 1, KB = 16;
     int64_t K = 1;
     double *partials = nullptr;  // kBpdnSums doubles per workgroup
@@ -84,6 +100,9 @@ template <typename T> int launch_bpdn_joint_apply(hipStream_t st, const BpdnArgs
 template <typename T>
 void launch_bpdn_joint_rows(hipStream_t st, const double *rowp, int nb, int M, int mode, T mr, T *rowf, double *out,
                             int slot);
+// out (M, K) = proj_l1(v (M, K), gamma, axis=0), device arrays, M <= kBpdnMaxDim, by the column search of the
+// projection mode on (M, KB) tiles, KB = bpdn_kb<T>(M, 1).  Returns the workgroups.
+template <typename T> int launch_bpdn_proj_cols(hipStream_t st, const T *v, T *out, int M, int64_t K, double gamma);
 // partials[0..2] = sum (D^T (D X) + c X - B)^2, (...)^2 of the left side, B^2 with B = bsave.  Returns the workgroups.
 template <typename T> int launch_bpdn_lsc(hipStream_t st, const BpdnArgs<T> &a);
 

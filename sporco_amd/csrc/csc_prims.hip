@@ -257,6 +257,17 @@ void prim_proj_l1(int64_t outer, int64_t P, int64_t inner, const void *v, double
     SA_HIP(hipMemcpy(out, dout.p, sizeof(T) * n, hipMemcpyDeviceToHost));
 }
 
+// proj_l1 of the columns of an (M, K) array by the column search of the bpdn handle's projection mode (csc_bpdn.h)
+template <typename T> void prim_proj_l1_cols(int M, int64_t K, const void *v, double gamma, void *out) {
+    const size_t bytes = sizeof(T) * (size_t)M * (size_t)K;
+    DevBuf dv(bytes), dout(bytes);
+    SA_HIP(hipMemcpy(dv.p, v, bytes, hipMemcpyHostToDevice));
+    SA_HIP(hipMemset(dout.p, 0xff, bytes));      // (NaN: an element the kernel does not write shows)
+    launch_bpdn_proj_cols<T>(nullptr, dv.as<T>(), dout.as<T>(), M, K, gamma);
+    SA_HIP(hipDeviceSynchronize());
+    SA_HIP(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+}
+
 template <typename T> void prim_rfl2norm2(int H, int W, int64_t P, const void *xf, double *out) {
     const int64_t npix = (int64_t)H * (W / 2 + 1);
     DevBuf dx(sizeof(cx<T>) * npix * P), dpart(sizeof(double) * kMaxPartialBlocks),
@@ -429,6 +440,14 @@ int sporco_amd_proj_l1(int dtype, int64_t outer, int64_t P, int64_t inner, const
     SA_API_BEGIN
     SA_REQUIRE(v && out && outer >= 1 && P >= 1 && inner >= 1 && gamma >= 0.0, "bad argument");
     SA_DISPATCH(dtype, prim_proj_l1, outer, P, inner, v, gamma, out)
+    SA_API_END
+}
+
+int sporco_amd_proj_l1_cols(int dtype, int32_t M, int64_t K, const void *v, double gamma, void *out) {
+    SA_API_BEGIN
+    SA_REQUIRE(v && out && M >= 1 && M <= SPORCO_AMD_BPDN_MAX_DIM && K >= 1 && K < ((int64_t)1 << 31) && gamma >= 0.0,
+               "proj_l1_cols: 1 <= M <= 512, 1 <= K < 2^31, gamma >= 0");
+    SA_DISPATCH(dtype, prim_proj_l1_cols, M, K, v, gamma, out)
     SA_API_END
 }
 
